@@ -7,7 +7,7 @@ in HBM (BASELINE configs[1]).  N > 1: one process per GPU (torch.distributed / R
 barrier and the max-over-ranks), every rank evaluates its own disjoint batch: weak scaling, no
 data-path collective (leaf evaluations are independent).
 
-    python bench.py [--gpus N --steps K --warmup W] [--dtype bf16|f16|f32] [--batch 512]
+    python bench.py [--gpus N --steps K --warmup W] [--dtype bf16|f16|f32] [--batch 512] [--dump-outputs DIR]
 
 The ONE JSON line carries, besides the contract's fields:
   roofline      the dominant kernel's achieved TFLOP/s (HIP events on the stream it runs on) vs the dense MFMA peak
@@ -23,6 +23,11 @@ The ONE JSON line carries, besides the contract's fields:
   configs0      (N = 1) BASELINE configs[0]'s shape on the engine: one game, 64 sims per move, batch-1 evaluations
 `value` is always the configs[1] kernel-path number; nothing in variants / end_to_end replaces it.  The timed output is
 checked after the timed region: sampled rows must equal, bit for bit, kh_infer_full of the same input.
+
+--dump-outputs DIR writes what the last timed step handed its caller (kh_infer_device's policy [B, 4672] and value
+tensor [B, 256], fp32) as DIR/policy.npy and DIR/value_full.npy; ranks > 0 add a _rank<r> suffix.  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.  Above DUMP_BYTES in all, a fixed
+seeded sample of rows (the same rows on every run) is written instead of the whole batch.
 """
 import argparse
 import ctypes as C
@@ -39,6 +44,22 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 PEAK_TFLOPS = {"bf16": 2500.0, "f16": 2500.0, "f32": 157.3}   # MI355X_MICROARCH.md, dense
+DUMP_BYTES = 64 << 20          # --dump-outputs: the most all ranks together write
+
+
+def dump_outputs(out_dir, outputs, B, rank, world):
+    """outputs: name -> device tensor [B, ...] (fp32).  Every rank writes its share of DUMP_BYTES; beyond that, the
+    rows of np.random.default_rng(0).choice(B, n) (sorted) stand for the batch."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    row_bytes = sum(t[0].numel() * 4 for t in outputs.values())
+    n = min(B, DUMP_BYTES // world // row_bytes)
+    rows = None if n == B else torch.from_numpy(np.sort(np.random.default_rng(0).choice(B, n, replace=False))).cuda()
+    suffix = "" if rank == 0 else f"_rank{rank}"
+    for name, t in outputs.items():
+        arr = (t if rows is None else t.index_select(0, rows)).float().cpu().numpy()
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), arr)
 
 
 def cpu_baseline(F, Cc, R, batch):
@@ -392,7 +413,10 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-variants", action="store_true", help="skip the variants / end_to_end legs (N = 1 only anyway)")
     ap.add_argument("--no-legs", action="store_true", help="skip value_f32 / encode / configs0 too: the headline kernel alone (profiler passes)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import numpy as np
     import torch
@@ -446,6 +470,8 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     dt = kd.max_over_ranks(dist, dt)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"policy": policy, "value_full": vfull}, B, rank, world)
     assert bool(torch.isfinite(policy).all()) and abs(float(policy[0].sum()) - 1.0) < 1e-2
     # the timed entry point against the host-buffer call of the same engine (the one the parity tests pin to the
     # reference's fixtures and the oracle): sampled rows, bit for bit

@@ -806,6 +806,18 @@ def test_rccl_backend_two_ranks(tmp_path):
     assert all(r["wgen"] == 41 and abs(r["wsum"] - float(ref.astype(np.float64).sum())) < 1e-9 for r in res)
 
 
+def _dropin_env(root):
+    """Environment for the drop-in binaries under oracle/_ref/dropin: this tree's kami_amd first on the library path.
+    Their rpath ($ORIGIN/../../../kami_amd) only holds while oracle/_ref sits inside this tree, and the binaries
+    may be built elsewhere and brought in; LD_LIBRARY_PATH is searched before the rpath, so the library they load
+    is always this checkout's."""
+    import os
+    env = dict(os.environ)
+    lib = os.path.join(root, "kami_amd")
+    env["LD_LIBRARY_PATH"] = lib + (os.pathsep + env["LD_LIBRARY_PATH"] if env.get("LD_LIBRARY_PATH") else "")
+    return env
+
+
 def test_reference_programs_on_the_cpp_mirror(tmp_path):
     """The reference's OWN test/nndisk.cpp, compiled unmodified against kami_amd/host/nn.h and
     libkamihip.so (make -C kami_amd/host dropin; binary under oracle/_ref/dropin, built in the build
@@ -815,7 +827,7 @@ def test_reference_programs_on_the_cpp_mirror(tmp_path):
     exe = os.path.join(root, "oracle", "_ref", "dropin", "test_nndisk")
     if not os.path.exists(exe):
         pytest.skip("drop-in binaries not built (needs the reference tree at build time)")
-    r = subprocess.run([exe], cwd=tmp_path, capture_output=True, text=True, timeout=300)
+    r = subprocess.run([exe], cwd=tmp_path, env=_dropin_env(root), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr
     assert "mismatch" not in r.stderr and "mismatch" not in r.stdout
     assert "Saved model to" in r.stdout
@@ -830,7 +842,7 @@ def test_reference_nntrain_program_on_the_cpp_mirror(tmp_path):
     exe = os.path.join(root, "oracle", "_ref", "dropin", "test_nntrain")
     if not os.path.exists(exe):
         pytest.skip("drop-in binaries not built (needs the reference tree at build time)")
-    r = subprocess.run([exe], cwd=tmp_path, capture_output=True, text=True, timeout=600)
+    r = subprocess.run([exe], cwd=tmp_path, env=_dropin_env(root), capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr + r.stdout
     m = re.search(r"Generated model 1, average loss ([-0-9.e+]+) to ([-0-9.e+]+) over 8 epochs", r.stdout)
     assert m, r.stdout
@@ -860,7 +872,7 @@ def test_reference_kami_program_full_cycle_on_the_cpp_mirror(tmp_path, program):
                 training_mlr=5, evaluate_batch=8, evaluate_games=8, evaluate_nodes=8, evaluate_target_pct=0,
                 model_path=str(tmp_path / "model.bin"), engine_dtype="bf16")
     (tmp_path / "options.yml").write_text("".join(f"{k}: {v}\n" for k, v in opts.items()))
-    proc = subprocess.Popen([exe], cwd=tmp_path, stdin=subprocess.PIPE, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    proc = subprocess.Popen([exe], cwd=tmp_path, env=_dropin_env(root), stdin=subprocess.PIPE, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     lines = []
     t = threading.Thread(target=lambda: lines.extend(iter(proc.stdout.readline, "")), daemon=True)
     t.start()
@@ -903,7 +915,7 @@ def test_kami_native_two_evaluators_in_one_process(tmp_path):
                 training_mlr=5, evaluate_batch=8, evaluate_games=8, evaluate_nodes=8, evaluate_target_pct=0,
                 model_path=str(tmp_path / "model.bin"), engine_dtype="bf16", engine_devices=2)
     (tmp_path / "options.yml").write_text("".join(f"{k}: {v}\n" for k, v in opts.items()))
-    proc = subprocess.Popen([exe], cwd=tmp_path, stdin=subprocess.PIPE, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    proc = subprocess.Popen([exe], cwd=tmp_path, env=_dropin_env(root), stdin=subprocess.PIPE, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     lines = []
     t = threading.Thread(target=lambda: lines.extend(iter(proc.stdout.readline, "")), daemon=True)
     t.start()
@@ -972,7 +984,7 @@ def test_configs0_literal_one_game_64_sims(tmp_path, program):
     opts = dict(filters=8, residuals=1, selfplay_batch=1, selfplay_nodes=64, inference_threads=1, training_threads=0,
                 replaybuffer_size=4096, model_path=str(tmp_path / "ref.pt"), engine_dtype="bf16")
     (tmp_path / "options.yml").write_text("".join(f"{k}: {v}\n" for k, v in opts.items()))
-    proc = subprocess.Popen([exe], cwd=tmp_path, stdin=subprocess.PIPE, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    proc = subprocess.Popen([exe], cwd=tmp_path, env=_dropin_env(root), stdin=subprocess.PIPE, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     lines = []
     t = threading.Thread(target=lambda: lines.extend(iter(proc.stdout.readline, "")), daemon=True)
     t.start()
