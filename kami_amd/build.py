@@ -25,9 +25,6 @@ SOURCES = ["kh_api.hip", "encode.hip", "forward_simple.hip", "tower_mfma.hip", "
 # MFMA results in arch VGPRs: the epilogues read them with VALU ops and would otherwise pay a
 # v_accvgpr_read per value (the kernel runs one wave per SIMD, registers are not scarce).
 EXTRA_FLAGS = {"tower_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "tower8_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"]}
-# (tools/wide_stamps.py and tools/t128_stamps.py use a separate diagnostic object of layers_mfma.hip built with
-#  -DKAMI_WIDE_DIAG — in-kernel s_memtime stamps — linked into csrc/build/libkamihip_diag.so by tools/build_diag.sh;
-#  the shipped library never contains it, and tower_mfma.hip has no diagnostic variants any more.)
 HIPCC_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-result", "-Wno-pass-failed",
                "-ffp-contract=fast"]
 

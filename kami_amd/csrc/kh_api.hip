@@ -2014,7 +2014,6 @@ int kh_set_coalesce(kh_engine* e, int target_batch, int max_wait_us)
 int kh_set_coalesce_callers(kh_engine* e, int callers)
 {
     if (!e || callers < 0 || callers > KH_MAX_OUTSTANDING) return fail(KH_ERR_INVALID, "callers in [0, %d]", KH_MAX_OUTSTANDING);
-    if (callers > 0 && getenv("KAMI_CO_CALLERS") && atoi(getenv("KAMI_CO_CALLERS")) > 0) callers = std::min(callers, atoi(getenv("KAMI_CO_CALLERS")));   // A/B knob: seal at fewer submissions
     e->co_callers = callers;
     if (e->co) { e->co->submits.fetch_add(1); e->co->cv_lane.notify_all(); }
     return KH_OK;

@@ -25,6 +25,7 @@
 #include <atomic>
 #include <cstdlib>
 #include <type_traits>
+#include <utility>
 
 namespace kh {
 namespace lay {
@@ -36,9 +37,6 @@ using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
 using f32x4s = __attribute__((ext_vector_type(4))) float;
 
-#ifndef KAMI_WIDE_BUFA
-#define KAMI_WIDE_BUFA 1           // tower2b / tower2s weight fragments by buffer loads (0: global loads, the A/B baseline)
-#endif
 // the policy heads' softmax (policy_head4_kernel and tower128_kernel<T, true>: one arithmetic, every batch size): v_exp_f32 /
 // v_log_f32 forms (2 ulp) instead of ocml's expf / logf — 256 calls per lane were 8-10 us of a 28 us head
 #ifndef KAMI_HEAD_FAST_EXP
@@ -118,15 +116,6 @@ __global__ __launch_bounds__(256) void planes_to_act_kernel(const float* __restr
     }
 }
 
-#ifdef KAMI_WIDE_DIAG
-// diagnostic build only (tools/wide_stamps.py): where a workgroup of the 3x3 skip layer spends its time
-__device__ unsigned long long g_wide_stamps[2048 * 8];
-#define WIDE_STAMP(k) do { if (TAPS == 9 && EPI == 1 && tid == 0 && blockIdx.x + gridDim.x * blockIdx.y < 2048) \
-    g_wide_stamps[(blockIdx.x + gridDim.x * blockIdx.y) * 8 + (k)] = (k) == 7 ? (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) : __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define WIDE_STAMP(k) do {} while (0)
-#endif
-
 struct ConvArgs {
     const unsigned short* in;     // T [B][64][Ci]
     const unsigned short* w;      // packed fragments [Co/64][taps][Ci/16][2][64 lanes][8]
@@ -178,10 +167,10 @@ __device__ __forceinline__ void ring_issue(const char* stream, int nch, int c, i
 // run-time loop hipcc rotated the double buffer through v_mov copies and issued the next chunk's
 // activation reads (behind a run-time address computation) at the END of a step, exposing their
 // latency after every barrier: 2.6x the tower's time per step.
-// RDN = ring slots.  RDN == 2 (3x3 layers with 128 input channels): ring + image = 81 664 B, so TWO workgroups
+// RDN = ring slots.  RDN == 2 (3x3 layers with more workgroups than CUs): ring + a 128-channel image = 81 664 B, so TWO workgroups
 // share a CU (256 registers each) and one's staging / epilogue runs under the other's MFMAs — with one
 // workgroup per CU all CUs stage at the same moment (42 % of a workgroup's time at 128 channels,
-// tools/wide_stamps.py) and then leave the memory system idle.  A 2-slot ring refills the slot of the chunk
+// DESIGN.md 5.3) and then leave the memory system idle.  A 2-slot ring refills the slot of the chunk
 // that is already in registers (AHEAD), so its reads must have completed before the step's barrier.
 // NP = passes over the input channels, CPT * 64 of them each: the image of one pass is 1/NP the size (256
 // channels as 2 x 128: two workgroups per CU there too; passes of 64 channels: image + ring = 50 944 B, THREE
@@ -206,8 +195,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, RDN == 2
     constexpr int NCH = TAPS * CPT, NCHT = NP * NCH;
     const char* stream = reinterpret_cast<const char*>(a.w) + (size_t)cb * NCHT * CHUNKB;
     char* img = smem + LDS_IMG;
-    WIDE_STAMP(0);
-    WIDE_STAMP(7);
 
     // weight stream first: the ring fills while the boards are staged
 #pragma unroll
@@ -295,9 +282,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, RDN == 2
         if (pass > 0) __syncthreads();                     // everybody is done reading the previous pass's image
         stage(pass);
         // image staged + first chunk of the pass landed, for everybody
-        if (pass == 0) WIDE_STAMP(1);
         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(2 * (RDN - 2 + AHEAD)) : "memory");
-        if (pass == 0) WIDE_STAMP(2);
         {
             const unsigned a_off = (unsigned)(((pass * NCH) % RDN) * CHUNKB) + lane * 16;
 #pragma unroll
@@ -333,9 +318,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, RDN == 2
             }
         }
     }
-    WIDE_STAMP(3);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // drain the ring (tail re-fetches) before exit
-    WIDE_STAMP(4);
 
     // ---- epilogue
     const int b = b0 + wb;
@@ -397,7 +380,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, RDN == 2
         out.w = to_bits<T>(v[6]) | ((unsigned)to_bits<T>(v[7]) << 16);
         *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned short*>(a.out) + o) = out;
     }
-    WIDE_STAMP(5);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -418,7 +400,6 @@ template <typename T, int EPI, int NP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv4_mfma_kernel(ConvArgs a)
 {
     constexpr int RDN = 4;
-    [[maybe_unused]] constexpr int TAPS = 9;              // WIDE_STAMP's condition
     constexpr int LDS_IMG = RDN * CHUNKB;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     using V = typename Elem<T>::vec8;
@@ -432,8 +413,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     constexpr int NCH = 2 * 9 * 2, NCHT = NP * NCH;        // 8 KB chunks per pass: 2 slices x 9 taps x 2 halves of 2 k-steps
     const char* stream = reinterpret_cast<const char*>(a.w) + (size_t)cb * NCHT * CHUNKB;
     char* img = smem + LDS_IMG;
-    WIDE_STAMP(0);
-    WIDE_STAMP(7);
 
 #pragma unroll
     for (int i = 0; i < RDN - 1; ++i) ring_issue<RDN>(stream, NCHT, i, wave, lane);
@@ -495,9 +474,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     for (int pass = 0; pass < NP; ++pass) {
         if (pass > 0) __syncthreads();                     // everybody is done reading the previous pass's image
         stage(pass);
-        if (pass == 0) WIDE_STAMP(1);
         asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)\n\ts_barrier" ::"n"(2 * (RDN - 2)) : "memory");
-        if (pass == 0) WIDE_STAMP(2);
         {
             const unsigned a_off = (unsigned)(((pass * NCH) % RDN) * CHUNKB) + lane * 16;
 #pragma unroll
@@ -536,9 +513,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
         }
     }
-    WIDE_STAMP(3);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // drain the ring (tail re-fetches) before exit
-    WIDE_STAMP(4);
 
     // ---- epilogue, registers -> HBM.  Lane (pixel, h) holds channels 32 ms + 8 g + 4 h + 0..3: after ReLU (+ skip, in
     // fp32 like nn.cpp:31) and rounding, groups g = 2j / 2j + 1 are exchanged between the lane halves so that lane
@@ -576,7 +551,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
         }
     }
-    WIDE_STAMP(5);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -589,14 +563,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // operand the per-layer path re-reads from HBM), round, write the board's next input image in place (the wave's own
 // LDS operations are ordered; its MFMAs have all read the old image by then) — and the weight ring simply runs on
 // through all (1 + 2R) x 36 chunks.  Same reduction order and epilogue arithmetic as the per-layer kernels: same bits.
-#ifdef KAMI_WIDE_DIAG
-// diagnostic build only: per layer, wave 0 of the first 256 workgroups stamps loop start / loop end / boundary end
-__device__ unsigned long long g_t128_stamps[256 * 64 * 4];
-#define T128_STAMP(l, k) do { if (tid == 0 && blockIdx.x < 256 && (l) < 64) g_t128_stamps[(blockIdx.x * 64 + (l)) * 4 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define T128_STAMP(l, k) do {} while (0)
-#endif
-
 struct Head4Args {
     const unsigned short* x;      // T [B][64][Ci], Ci = NP * 128
     const unsigned short* w;      // policyconv chunks (Ci / 32 of 8 KB) then policyconv2 chunks (4), pack_layer_wide128 order
@@ -801,7 +767,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 }
     };
     for (int l = 0; l < NL; ++l) {
-        T128_STAMP(l, 0);
 #pragma unroll
         for (int k = 0; k < 2; ++k)
 #pragma unroll
@@ -838,13 +803,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             }
             __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
         }
-        T128_STAMP(l, 1);
         if (l == 0) boundary(std::integral_constant<int, 0>{});
         else if (l & 1) boundary(std::integral_constant<int, 1>{});
         else boundary(std::integral_constant<int, 2>{});
-        T128_STAMP(l, 3);
         shift_to_acc();
-        T128_STAMP(l, 2);
     }
     if constexpr (HEAD) {
         // ---- both heads (nn.cpp:72-88) on this wave's board, policy_head4_kernel<T, 1>'s arithmetic in its order.  The image
@@ -920,10 +882,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
             }
         };
-        T128_STAMP(NL, 0);
         init_acc(hd.shift1);
         four_steps(NCHT);
-        T128_STAMP(NL, 1);
         // policyconv's output (pbatchnorm folded, ReLU, rounded to T) -> this wave's image, in place
 #pragma unroll
         for (int hp = 0; hp < 2; ++hp)
@@ -938,7 +898,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
                 }
         init_acc(hd.bias2);
         four_steps(NCHT + 4);
-        T128_STAMP(NL, 2);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // drain the ring (tail re-fetches) before its memory is reused
         // ---- softmax over the board's 64 pixels x 73 planes, all inside this wave
         const int b = b0 + wave;
@@ -963,7 +922,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         sum = wave_sum_f(sum);
         const float ls = HEAD_LOG(sum);
         const bool row_nan = __any(nan);
-        T128_STAMP(NL, 3);
         __syncthreads();                                   // ring and images are dead: the rows go through their memory
         float* rowbuf = reinterpret_cast<float*>(smem) + wave * KH_PSIZE;
         const bool live = b < a.B;
@@ -988,7 +946,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
         };
         if (hd.logits) put_row(hd.logits + (size_t)(live ? b : 0) * KH_PSIZE, false);
         put_row(hd.policy + (size_t)(live ? b : 0) * KH_PSIZE, true);
-        T128_STAMP(NL + 1, 0);
         if (!live) return;
         if (row_nan && lane == 0) atomicOr(&hd.flags[0], 1);
         if (hd.vw) {
@@ -1022,7 +979,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             if (vnan) atomicOr(&hd.flags[1], 1);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        T128_STAMP(NL + 1, 1);
         return;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // drain the ring (tail re-fetches) before exit
@@ -1097,7 +1053,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, CH == 12
     // requested NA k-steps ahead: 4 x 256 clocks of MFMAs at 256 channels, 8 x 128 at 128 — an L2 round trip under load
     constexpr int NA = KAMI_T2B_NA;                          // k-steps of weight fragments in flight (8 bought nothing at 128 channels and cost the second workgroup per CU its registers)
     V Areg[NA][MSW];
-#if KAMI_WIDE_BUFA
     // buffer loads: descriptor in SGPRs, the k-step's byte offset in ONE SGPR, the lane offset a loop-invariant VGPR — one
     // scalar add and the load per k-step (the global_load form cost seven scalar instructions and a v_mov per step, and a
     // 4-MFMA step is issue-bound with one wave per SIMD: 20x256 batch 256 with the weight loads removed 622 -> 487 us).
@@ -1108,15 +1063,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, CH == 12
         for (int ms = 0; ms < MSW; ++ms)
             Areg[slot][ms] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, wlane + ms * 1024, k * KSB, 0));
     };
-#else
-    auto load_a = [&](int slot, int k) {
-        const size_t kc = (size_t)(k < NKT ? k : NKT - 1) * KSB;         // past the end: a harmless re-read
-        unsigned vo = wlane;
-        asm volatile("" : "+v"(vo));                         // keeps the lane offset out of a hoisted 64-bit vector base
-#pragma unroll
-        for (int ms = 0; ms < MSW; ++ms) Areg[slot][ms] = *reinterpret_cast<const V*>(wl + kc + ms * 1024 + vo);
-    };
-#endif
 #pragma unroll
     for (int j = 0; j < NA; ++j) load_a(j, j);
     {
@@ -1239,7 +1185,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, CH == 12
     };
     int k0 = 0;
     for (int l = 0; l < NL; ++l) {
-        T128_STAMP(l, 0);
 #pragma unroll
         for (int j = 0; j < NBS - 1; ++j)
 #pragma unroll
@@ -1251,15 +1196,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, CH == 12
             else slice_steps(k0, q, std::integral_constant<int, 4>{});
             k0 += 36;
         }
-        T128_STAMP(l, 1);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // every wave has read what it needs of the old image
         if (l == 0) boundary(std::integral_constant<int, 0>{});
         else if (l & 1) boundary(std::integral_constant<int, 1>{});
         else boundary(std::integral_constant<int, 2>{});
-        T128_STAMP(l, 3);
         load_shift(l + 1);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");      // the new image is complete
-        T128_STAMP(l, 2);
     }
 #pragma unroll
     for (int pt = 0; pt < 4; ++pt) {
@@ -1296,12 +1238,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, CH == 12
 // (tower2b<T,128>'s step); 6 waves on 4 SIMDs, so at most 256 registers (it needs ~190).  Bounded spin: a partner that
 // does not show up within a second raises the policy NaN flag (the call fails) instead of hanging the device; with at most
 // one workgroup per CU and no more workgroups than CUs every partner is resident or becomes so.
-#ifdef KAMI_WIDE_DIAG
-__device__ unsigned long long g_t2s_stamps[256 * 64 * 8];
-#define T2S_STAMP(l, k) do { if (lane == 0 && blockIdx.x < 256 && (l) < 64) g_t2s_stamps[(blockIdx.x * 64 + (l)) * 8 + (k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define T2S_STAMP(l, k) do {} while (0)
-#endif
 struct Tower2sArgs {
     const float* planes;          // fp32 [B][64][F], F <= 128, 16-byte aligned
     int F;
@@ -1314,7 +1250,6 @@ struct Tower2sArgs {
     unsigned* xflag;              // [npairs][2] flags, 64 bytes apart; zeroed by the launcher before every launch
     int* flags;                   // the engine's NaN flags ([0] is raised on an exchange time-out, [3] = 'X')
     int npairs;
-    int abl;                      // timing-only ablations (KAMI_T2S_ABL): 1 no global exchange, 2 no mover copies at all
 };
 
 template <typename T>
@@ -1390,10 +1325,9 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
             return (unsigned)(bb * board_bytes + (((pp >> 3) + 1) * PITCH + (pp & 7) + 1) * stride + hh * 256) + lane_b;
         };
         for (int l = 0; l < NL; ++l) {
-            if (l > 0 && !(a.abl & 2)) {
+            if (l > 0) {
                 // the partner's channels of layer l - 1's output: epoch l in its flag
                 bool ok = true;
-                if (!(a.abl & 1))
                 if (lane == 0) {
                     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
                     while (__hip_atomic_load(itsflag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < (unsigned)l) {
@@ -1402,7 +1336,6 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
                     }
                     if (!ok) { atomicOr(&a.flags[0], 1); a.flags[3] = 'X'; }
                 }
-                if (hw == 0) T2S_STAMP(l, 6);
                 const unsigned short* src = a.xbuf + ((size_t)(((l - 1) & 1) * a.npairs + pair) * 2 + (half ^ 1)) * half_elems;
                 const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned short*>(src), 0, (int)(half_elems * 2), 0x00020000);
                 {
@@ -1412,9 +1345,7 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
 #pragma unroll
                     for (int k = 0; k < 16; ++k) {
                         const int p = hw * 64 + k * 4 + lane_px;
-                        if (!(a.abl & 1)) r[k] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, p * 256 + lane_b, 0, 16);        // aux 16 = sc1
-                        else r[k] = u32x4{ 0, 0, 0, 0 };
-                        if (a.abl & 4) __builtin_amdgcn_s_sleep(1);      // paced: the compute waves' weight loads go through the same L1
+                        r[k] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, p * 256 + lane_b, 0, 16);        // aux 16 = sc1
                     }
 #pragma unroll
                     for (int k = 0; k < 16; ++k) {
@@ -1422,15 +1353,12 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
                         *reinterpret_cast<u32x4*>(smem + lds_off(p, half ^ 1)) = r[k];
                     }
                 }
-            }
-            if (l > 0) {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                if (hw == 0) T2S_STAMP(l, 7);
                 asm volatile("s_barrier" ::: "memory");                                                      // [X]
             }
             asm volatile("s_barrier" ::: "memory");                                                          // [R]
             asm volatile("s_barrier" ::: "memory");                                                          // [W]
-            if (l + 1 < NL && !(a.abl & 2)) {
+            if (l + 1 < NL) {
                 unsigned short* dst = a.xbuf + ((size_t)((l & 1) * a.npairs + pair) * 2 + half) * half_elems;
                 const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(dst, 0, (int)(half_elems * 2), 0x00020000);
                 {
@@ -1443,13 +1371,11 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
 #pragma unroll
                     for (int k = 0; k < 16; ++k) {
                         const int p = hw * 64 + k * 4 + lane_px;
-                        if (!(a.abl & 1)) __builtin_amdgcn_raw_buffer_store_b128(r[k], rsrc, p * 256 + lane_b, 0, 16);         // write-through
-                        if (a.abl & 4) __builtin_amdgcn_s_sleep(1);
+                        __builtin_amdgcn_raw_buffer_store_b128(r[k], rsrc, p * 256 + lane_b, 0, 16);         // write-through
                     }
                 }
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                             // drained: then the flag
                 if (lane == 0) __hip_atomic_store(myflag, (unsigned)(l + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if (hw == 0) T2S_STAMP(l + 1, 5);
             }
         }
         return;
@@ -1461,19 +1387,10 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     constexpr int NA = KAMI_T2S_NA;                          // k-steps of weight fragments in flight
     static_assert(36 % NA == 0, "a slice's first k-step must land on slot 0");
     V Areg[NA];
-#if KAMI_WIDE_BUFA
     const auto a_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(wl), 0, NKT * KSB - rt * 1024, 0x00020000);   // (see tower2b_kernel)
     auto load_a = [&](int slot, int k) {
         Areg[slot] = __builtin_bit_cast(V, __builtin_amdgcn_raw_buffer_load_b128(a_rsrc, wlane, k * KSB, 0));
     };
-#else
-    auto load_a = [&](int slot, int k) {
-        const size_t kc = (size_t)(k < NKT ? k : NKT - 1) * KSB;         // past the end: a harmless re-read
-        unsigned vo = wlane;
-        asm volatile("" : "+v"(vo));
-        Areg[slot] = *reinterpret_cast<const V*>(wl + kc + vo);
-    };
-#endif
 #pragma unroll
     for (int j = 0; j < NA; ++j) load_a(j, j);
     const int lp = PIXMAP[lane & 31];
@@ -1515,15 +1432,11 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
             const int m = n + NBS - 1;
             const unsigned off = m < 36 ? kstep_off(m) + q * 128 : kstep_off(m - 36) + qnext * 128;
             __builtin_amdgcn_sched_barrier(0);               // a step's loads stay in their step
-#if !defined(KAMI_T2S_NOB)
 #pragma unroll
             for (int pt = 0; pt < 4; ++pt) Bq[nxt][pt] = *reinterpret_cast<const V*>(smem + b_base + tile_off(pt) + off);
-#endif
 #pragma unroll
             for (int pt = 0; pt < 4; ++pt) acc[pt] = Elem<T>::mfma(Areg[slot], Bq[cur][pt], acc[pt]);
-#if !defined(KAMI_T2S_NOA)
             load_a(slot, n + NA < 36 ? kcur + n + NA : knext + n + NA - 36);
-#endif
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
@@ -1565,13 +1478,10 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
     auto kbase_of = [&](int l) -> int { return l == 0 ? 0 : 72 + (l - 1) * 144; };
     for (int l = 0; l < NL; ++l) {
         const int ns = l == 0 ? 2 : 4;
-        if (wave == 0) T2S_STAMP(l, 0);
         preload_b(slice_of(l, 0));
         for (int i = 0; i < ns; ++i) {
             if (l > 0 && i == 2) {
-                if (wave == 0) T2S_STAMP(l, 1);
                 asm volatile("s_barrier" ::: "memory");                                   // [X]
-                if (wave == 0) T2S_STAMP(l, 2);
                 preload_b(slice_of(l, 2));                   // (what the previous slice prefetched here was not the partner's yet)
             }
             const int q = slice_of(l, i);
@@ -1580,14 +1490,12 @@ __global__ __launch_bounds__(384) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
             const int kcur = kbase_of(l) + q * 36, knext = (last ? kbase_of(l + 1) : kbase_of(l)) + qn * 36;
             slice_steps(kcur, knext, q, qn);
         }
-        if (wave == 0) T2S_STAMP(l, 3);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                   // [R]
         if (l == 0) boundary(std::integral_constant<int, 0>{});
         else if (l & 1) boundary(std::integral_constant<int, 1>{});
         else boundary(std::integral_constant<int, 2>{});
         load_shift(l + 1);
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");                   // [W]
-        if (wave == 0) T2S_STAMP(l, 4);
     }
 #pragma unroll
     for (int pt = 0; pt < 4; ++pt) {
@@ -2165,26 +2073,25 @@ __global__ __launch_bounds__(256) void value_conv_f32_kernel(const float* __rest
     }
 }
 
+// raises kernel K's dynamic-LDS limit to 160 KB before its first launch: once per process (engines are called from many
+// host threads; raising it twice is harmless)
+template <auto K> static hipError_t allow_lds()
+{
+    static std::atomic<bool> done{ false };
+    if (done.load(std::memory_order_acquire)) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e == hipSuccess) done.store(true, std::memory_order_release);
+    return e;
+}
+
 template <int TAPS, int EPI> static hipError_t launch_conv_f32(const ConvArgsF32& a, hipStream_t s)
 {
     const int lds = 2 * ((TAPS == 9) ? NPIX : 64) * ((a.Ci < 128 ? a.Ci : 128) * 4 + 16);
-    static std::atomic<bool> attr_done{ false };      // engines are called from many host threads; setting it twice is harmless
-    if (!attr_done.load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f32_kernel<TAPS, EPI>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_done.store(true, std::memory_order_release);
-    }
+    if (const hipError_t e = allow_lds<&conv_f32_kernel<TAPS, EPI>>(); e != hipSuccess) return e;
     // few boards (the trainer): one board x 32 channels per workgroup, the reduction split over its waves
     if constexpr (EPI == 3 || EPI == 4) {
         if ((long)((a.B + 1) / 2) * ((a.Co + 63) / 64) < 128) {
-            static std::atomic<bool> attr2_done{ false };
-            if (!attr2_done.load(std::memory_order_acquire)) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f32_small_kernel<TAPS, EPI>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) return e;
-                attr2_done.store(true, std::memory_order_release);
-            }
+            if (const hipError_t e = allow_lds<&conv_f32_small_kernel<TAPS, EPI>>(); e != hipSuccess) return e;
             const int lds1 = std::max(lds / 2, 2 * 64 * 16 * 4);
             hipLaunchKernelGGL((conv_f32_small_kernel<TAPS, EPI>), dim3(a.B, (a.Co + 31) / 32), dim3(256), lds1, s, a);
             return hipGetLastError();
@@ -2192,13 +2099,7 @@ template <int TAPS, int EPI> static hipError_t launch_conv_f32(const ConvArgsF32
     }
     if constexpr (EPI <= 2) {
         if (a.Ci <= 128 && a.Co % 64 == 0 && a.shift) {
-            static std::atomic<bool> attr3_done{ false };
-            if (!attr3_done.load(std::memory_order_acquire)) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_f32_kernel<TAPS, EPI, true>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) return e;
-                attr3_done.store(true, std::memory_order_release);
-            }
+            if (const hipError_t e = allow_lds<&conv_f32_kernel<TAPS, EPI, true>>(); e != hipSuccess) return e;
             hipLaunchKernelGGL((conv_f32_kernel<TAPS, EPI, true>), dim3((a.B + 1) / 2, a.Co / 64), dim3(256), lds, s, a);
             return hipGetLastError();
         }
@@ -2249,13 +2150,7 @@ template <typename T, int TAPS, int EPI, int CPT, int RDN, int NP = 1> static hi
     const int stride = CPT * 64 * 2 + 16;                  // image of one pass
     const int image = 2 * ((TAPS == 9) ? NPIX : 64) * stride, tiles = 4 * 32 * (64 * 4 + 16);   // the epilogue's transpose tiles reuse the image
     const int lds = RDN * CHUNKB + (image > tiles ? image : tiles);
-    static std::atomic<bool> attr_done{ false };      // engines are called from many host threads; setting it twice is harmless
-    if (!attr_done.load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_mfma_kernel<T, TAPS, EPI, CPT, RDN, NP>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_done.store(true, std::memory_order_release);
-    }
+    if (const hipError_t e = allow_lds<&conv_mfma_kernel<T, TAPS, EPI, CPT, RDN, NP>>(); e != hipSuccess) return e;
     hipLaunchKernelGGL((conv_mfma_kernel<T, TAPS, EPI, CPT, RDN, NP>), dim3((a.B + 1) / 2, a.Co / 64), dim3(256), lds, s, a);
     return hipGetLastError();
 }
@@ -2263,13 +2158,7 @@ template <typename T, int TAPS, int EPI, int CPT, int RDN, int NP = 1> static hi
 template <typename T, int EPI, int NP> static hipError_t launch_conv4(const ConvArgs& a, hipStream_t s)
 {
     const int lds = 4 * CHUNKB + 4 * NPIX * (128 * 2 + 16);          // 163 328 B: one workgroup per CU
-    static std::atomic<bool> attr_done{ false };
-    if (!attr_done.load(std::memory_order_acquire)) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv4_mfma_kernel<T, EPI, NP>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr_done.store(true, std::memory_order_release);
-    }
+    if (const hipError_t e = allow_lds<&conv4_mfma_kernel<T, EPI, NP>>(); e != hipSuccess) return e;
     ConvArgs b = a;
     b.w = a.w4;
     hipLaunchKernelGGL((conv4_mfma_kernel<T, EPI, NP>), dim3((a.B + 3) / 4, a.Co / 128), dim3(256), lds, s, b);
@@ -2278,28 +2167,20 @@ template <typename T, int EPI, int NP> static hipError_t launch_conv4(const Conv
 
 template <typename T, int TAPS, int EPI, int CPT> static hipError_t launch_conv_cpt(const ConvArgs& a, hipStream_t s)
 {
-    // 3x3 layers with more workgroups than CUs: the 2-slot-ring variants, two workgroups per CU (128 input
-    // channels; 256 as two passes of 128) or three (passes of 64 channels) when there are enough of them.
-    // 10x128 at batch 1024: 726 -> 600 us per forward with two; with one workgroup per CU anyway the short ring
-    // only costs (219 -> 251 us at batch 256), so this is decided per launch.
-    const long wgs = (long)((a.B + 1) / 2) * (a.Co / 64);
-    static const int force = getenv("KAMI_WIDE_VARIANT") ? atoi(getenv("KAMI_WIDE_VARIANT")) : 0;   // experiments: 1, 2, 3 workgroups per CU; 4 = four boards per workgroup
-    // four boards x 128 output channels per workgroup (conv4_mfma_kernel) once that still gives every CU a workgroup
-    if constexpr (TAPS == 9 && EPI != 2 && (CPT == 2 || CPT == 4)) {
-        const long wg4 = (long)((a.B + 3) / 4) * (a.Co / 128);
-        if (a.w4 && a.Co % 128 == 0 && (force == 4 || (!force && wg4 >= 256))) return launch_conv4<T, EPI, CPT / 2>(a, s);
-    }
-    // measured (tools/wide_variants.py): 128 channels: three per CU is ahead from 512 workgroups on (+2 %, +14 % at
-    // 2048); 256 channels: two and three are within 2 % of each other either way
-    if constexpr (TAPS == 9 && CPT == 2) {
-        const int per_cu = force ? force : (wgs > 256 ? 3 : 1);
-        if (per_cu == 3) return launch_conv_rd<T, TAPS, EPI, 1, 2, 2>(a, s);
-        if (per_cu == 2) return launch_conv_rd<T, TAPS, EPI, 2, 2>(a, s);
-    }
-    if constexpr (TAPS == 9 && CPT == 4) {
-        const int per_cu = force ? force : (wgs > 256 ? 2 : 1);
-        if (per_cu == 3) return launch_conv_rd<T, TAPS, EPI, 1, 2, 4>(a, s);
-        if (per_cu == 2) return launch_conv_rd<T, TAPS, EPI, 2, 2, 2>(a, s);
+    if constexpr (TAPS == 9) {
+        // four boards x 128 output channels per workgroup (conv4_mfma_kernel) once that still gives every CU a workgroup
+        if constexpr (EPI != 2 && (CPT == 2 || CPT == 4)) {
+            const long wg4 = (long)((a.B + 3) / 4) * (a.Co / 128);
+            if (a.w4 && a.Co % 128 == 0 && wg4 >= 256) return launch_conv4<T, EPI, CPT / 2>(a, s);
+        }
+        // more workgroups than CUs: the 2-slot-ring variants, several workgroups per CU.  With one round of workgroups
+        // anyway the short ring only costs (10x128 at batch 256: 219 -> 251 us), so this is decided per launch.
+        // 128 channels: three per CU (passes of 64) is ahead of one from 512 workgroups on (10x128 at batch 1024: 726 ->
+        // 600 us with two, 596 with three; batch 2048 +14 % for three over two).  256 channels: two per CU (passes of 128);
+        // three are within 2 % of two either way.
+        const long wgs = (long)((a.B + 1) / 2) * (a.Co / 64);
+        if constexpr (CPT == 2) if (wgs > 256) return launch_conv_rd<T, TAPS, EPI, 1, 2, 2>(a, s);
+        if constexpr (CPT == 4) if (wgs > 256) return launch_conv_rd<T, TAPS, EPI, 2, 2, 2>(a, s);
     }
     return launch_conv_rd<T, TAPS, EPI, CPT, RD>(a, s);
 }
@@ -2315,160 +2196,159 @@ template <typename T, int TAPS, int EPI> static hipError_t launch_conv(const Con
     }
 }
 
-template <typename T> static hipError_t run(const LayersArgs& L, hipStream_t s)
+// What one bf16 / f16 forward launches, decided from the shapes alone (run<T> carries it out)
+enum class Plan {
+    Tower128Fused,   // tower128_kernel, the heads inside its launch when they are packed for it (L.wh)
+    Tower2b,         // tower2b_kernel (128 or 256 filters), then the heads
+    Tower2s,         // tower2s_kernel (256 filters), then the heads
+    PerLayer,        // planes_to_act_kernel, one launch per convolution, then the heads
+};
+
+// tower2s_kernel's workgroups: the two halves of board pair g are blocks g and g ^ 8, so whole groups of eight pairs
+static int tower2s_grid(int B) { return 16 * (((B + 1) / 2 + 7) / 8); }
+
+static Plan choose_plan(const LayersArgs& L)
 {
-    const long npix = (long)L.B * 64;
-    int blocks = (int)((npix * (L.FP / 8) + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    static const int force = getenv("KAMI_WIDE_VARIANT") ? atoi(getenv("KAMI_WIDE_VARIANT")) : 0;
-    // 128 planes (padded) and 128 filters: the whole 3x3 stack in one launch, activations on chip (tower128_kernel),
-    // reading the fp32 planes itself.  One workgroup per four boards: worth it once that keeps most CUs busy.
-    const bool fused = L.FP == 128 && L.CP == 128 && L.w4 && L.w4_off[0] != (size_t)-1 && force != 6 && (force == 5 || (!force && L.B >= 640));
-    const bool direct = fused && (reinterpret_cast<uintptr_t>(L.in) & 15) == 0;
-    // two boards per workgroup, waves own output channels (tower2b_kernel): 256 filters from batch 256 on; 128 filters
-    // for the batches where tower128_kernel's four boards per workgroup do not fill the chip (KAMI_WIDE_VARIANT=6 forces it).
-    // It reads the fp32 planes itself: ONE condition decides both that and whether planes_to_act_kernel runs (they used to
-    // disagree for 256 filters at 256 <= batch < 384: a launch whose output nobody read).
+    // the whole-tower kernels stage the fp32 planes themselves (16-byte loads); tower128_kernel can also take them from
+    // planes_to_act_kernel
     const bool aligned = (reinterpret_cast<uintptr_t>(L.in) & 15) == 0;
-    // 256 filters, up to one board pair per TWO CUs: two workgroups per pair, each half the output channels, halves
-    // exchanged per layer (tower2s_kernel; KAMI_WIDE_VARIANT=7 forces it, 6 keeps tower2b_kernel).  Every workgroup must
-    // be resident (partners wait for each other): never more workgroups than CUs.
-    const int pairs = (L.B + 1) / 2, grid2s = 16 * ((pairs + 7) / 8);
-    const bool split = aligned && L.FP == 128 && L.CP == 256 && L.w2b && L.xbuf && L.xflag && pairs <= L.x_pairs && grid2s <= L.num_cus &&
-                       (force == 7 || (!force && L.B >= KAMI_SPLIT_MIN_B));
-    const bool fused256 = split || (aligned && L.FP == 128 && ((L.CP == 256 && L.w2b && (force == 6 || (!force && L.B >= 256))) ||
-                                                                (L.CP == 128 && L.w4 && L.w4_off[0] != (size_t)-1 && (force == 6 || (!force && L.B >= 256 && !fused)))));
-    static const bool dbg = getenv("KAMI_WIDE_DEBUG") != nullptr;
-    if (dbg) fprintf(stderr, "[kami wide] B %d FP %d CP %d aligned %d w2b %d xbuf %d x_pairs %d num_cus %d grid2s %d force %d -> split %d fused256 %d fused %d\n",
-                     L.B, L.FP, L.CP, (int)aligned, L.w2b != nullptr, L.xbuf != nullptr, L.x_pairs, L.num_cus, grid2s, force, (int)split, (int)fused256, (int)fused);
-    if (!direct && !fused256) hipLaunchKernelGGL(planes_to_act_kernel<T>, dim3(blocks), dim3(256), 0, s, L.in, L.act_in, npix, L.F, L.FP);
-    unsigned short *x = L.act[0], *t = L.act[1], *u = L.act[2];
+    if (L.FP != 128) return Plan::PerLayer;
+    if (L.CP == 128 && L.w4 && L.w4_off[0] != (size_t)-1) {
+        // 128 filters: four boards per workgroup, activations on chip, worth it once that keeps most CUs busy; two boards
+        // per workgroup (waves own output channels) for the batches where four do not fill the chip
+        if (L.B >= 640) return Plan::Tower128Fused;
+        if (L.B >= 256 && aligned) return Plan::Tower2b;
+    }
+    if (L.CP == 256 && L.w2b && aligned) {
+        // 256 filters, up to one board pair per TWO CUs: two workgroups per pair, each half the output channels, halves
+        // exchanged per layer.  Every workgroup must be resident (partners wait for each other): never more workgroups
+        // than CUs.  Above that, tower2b_kernel from batch 256 on.
+        if (L.xbuf && L.xflag && (L.B + 1) / 2 <= L.x_pairs && tower2s_grid(L.B) <= L.num_cus && L.B >= KAMI_SPLIT_MIN_B)
+            return Plan::Tower2s;
+        if (L.B >= 256) return Plan::Tower2b;
+    }
+    return Plan::PerLayer;
+}
+
+// conv + BN + ReLU, conv + bias and the softmax of the policy head, and the value head, on the residual stream `x`;
+// li: the index of the policy head's first layer
+static Head4Args head_args(const LayersArgs& L, const unsigned short* x, size_t li)
+{
+    Head4Args hd;
+    hd.x = x; hd.w = L.wh; hd.shift1 = L.shift + L.shift_off[li]; hd.bias2 = L.shift + L.shift_off[li + 1];
+    hd.policy = L.policy; hd.logits = L.want_logits ? L.logits : nullptr; hd.flags = L.flags; hd.B = L.B;
+    hd.vw = L.vw; hd.vshift = L.vshift; hd.fcw = L.fcw; hd.fcb = L.fcb; hd.fc4 = L.fc4; hd.vfull = L.vfull;
+    return hd;
+}
+
+template <typename T> static hipError_t run_heads(const LayersArgs& L, const unsigned short* x, size_t li, hipStream_t s)
+{
     hipError_t e;
-    size_t li = 0;
-    auto layer = [&](int idx) { return L.w + L.w_off[idx]; };
-    auto layer4 = [&](int idx) -> const unsigned short* { return (L.w4 && L.w4_off[idx] != (size_t)-1) ? L.w4 + L.w4_off[idx] : nullptr; };
-    auto shift = [&](int idx) { return L.shift + L.shift_off[idx]; };
-    ConvArgs a;
-    a.B = L.B;
-    if (fused256) {
-        static std::atomic<bool> attr_done{ false };
-        if (!attr_done.load(std::memory_order_acquire)) {
-            if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tower2b_kernel<T, 256>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-            if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tower2b_kernel<T, 128>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-            attr_done.store(true, std::memory_order_release);
-        }
-        if (split) {
-            static std::atomic<bool> attr2s_done{ false };
-            if (!attr2s_done.load(std::memory_order_acquire)) {
-                if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tower2s_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-                attr2s_done.store(true, std::memory_order_release);
-            }
-            // every polled word zero before every launch (a block of its own at the allocation's start, a multiple of 16 bytes)
-            if ((e = hipMemsetAsync(L.xflag, 0, layers_xflag_bytes(pairs), s)) != hipSuccess) return e;
-            Tower2sArgs t2;
-            t2.planes = L.in; t2.F = L.F; t2.magic = (unsigned)((0x100000000ull + L.F - 1) / L.F);
-            t2.w = L.w2b; t2.shift = shift(0); t2.out = x; t2.B = L.B; t2.R = L.R;
-            t2.xbuf = L.xbuf; t2.xflag = L.xflag; t2.flags = L.flags; t2.npairs = pairs;
-            static const int abl2s = getenv("KAMI_T2S_ABL") ? atoi(getenv("KAMI_T2S_ABL")) : 0;
-            t2.abl = abl2s;
-            hipLaunchKernelGGL((tower2s_kernel<T>), dim3(grid2s), dim3(384), 2 * NPIX * (256 * 2 + 16), s, t2);
-            if ((e = hipGetLastError()) != hipSuccess) return e;
-        } else {
-        Tower256Args t2;
-        t2.planes = L.in; t2.F = L.F; t2.magic = (unsigned)((0x100000000ull + L.F - 1) / L.F);
-        t2.w = L.CP == 256 ? L.w2b : layer4(0); t2.shift = shift(0); t2.out = x; t2.B = L.B; t2.R = L.R;
-        if (L.CP == 256) hipLaunchKernelGGL((tower2b_kernel<T, 256>), dim3((L.B + 1) / 2), dim3(256), 2 * NPIX * (256 * 2 + 16), s, t2);
-        else hipLaunchKernelGGL((tower2b_kernel<T, 128>), dim3((L.B + 1) / 2), dim3(256), 2 * NPIX * (128 * 2 + 16), s, t2);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-        }
-        li = 1 + 2 * (size_t)L.R;
-    }
-    if (fused && !fused256) {
-        static std::atomic<bool> attr_done{ false };
-        if (!attr_done.load(std::memory_order_acquire)) {
-            if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tower128_kernel<T, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-            if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tower128_kernel<T, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-            attr_done.store(true, std::memory_order_release);
-        }
-        Tower128Args t8;
-        t8.planes = direct ? L.in : nullptr; t8.F = L.F; t8.magic = (unsigned)((0x100000000ull + L.F - 1) / L.F);
-        t8.in = L.act_in; t8.w = layer4(0); t8.shift = shift(0); t8.out = x; t8.B = L.B; t8.R = L.R;
-        li = 1 + 2 * (size_t)L.R;
-        // both heads inside the same launch (KAMI_T128_HEAD=0: policy_head4_kernel behind it, the A/B baseline)
-        static const bool head_in = !(getenv("KAMI_T128_HEAD") && atoi(getenv("KAMI_T128_HEAD")) == 0);
-        if (head_in && L.wh && L.CP == 128) {
-            Head4Args& hd = t8.hd;
-            hd.x = nullptr; hd.w = L.wh; hd.shift1 = shift(li); hd.bias2 = shift(li + 1); hd.policy = L.policy; hd.logits = L.want_logits ? L.logits : nullptr;
-            hd.flags = L.flags; hd.B = L.B;
-            hd.vw = L.vw; hd.vshift = L.vshift; hd.fcw = L.fcw; hd.fcb = L.fcb; hd.fc4 = L.fc4; hd.vfull = L.vfull;
-            hipLaunchKernelGGL((tower128_kernel<T, true>), dim3((L.B + 3) / 4), dim3(256), 4 * CHUNKB + 4 * NPIX * (128 * 2 + 16), s, t8);
-            return hipGetLastError();
-        }
-        hipLaunchKernelGGL((tower128_kernel<T, false>), dim3((L.B + 3) / 4), dim3(256), 4 * CHUNKB + 4 * NPIX * (128 * 2 + 16), s, t8);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    }
-    // stem                                                                  nn.cpp:62-65
-    if (!fused && !fused256) {
-    a.in = L.act_in; a.w = layer(li); a.w4 = layer4(li); a.shift = shift(li); a.skip = nullptr; a.out = x; a.Ci = L.FP; a.Co = L.CP; ++li;
-    if ((e = launch_conv<T, 9, 0>(a, s)) != hipSuccess) return e;
-    }
-    for (int r = 0; r < ((fused || fused256) ? 0 : L.R); ++r) {           // nn.cpp:26-34
-        a.in = x; a.w = layer(li); a.w4 = layer4(li); a.shift = shift(li); a.skip = nullptr; a.out = t; a.Ci = L.CP; a.Co = L.CP; ++li;
-        if ((e = launch_conv<T, 9, 0>(a, s)) != hipSuccess) return e;
-        a.in = t; a.w = layer(li); a.w4 = layer4(li); a.shift = shift(li); a.skip = x; a.out = u; ++li;
-        if ((e = launch_conv<T, 9, 1>(a, s)) != hipSuccess) return e;
-        unsigned short* tmp = x; x = u; u = tmp;
-    }
-    // policy head                                                           nn.cpp:72-80
-    a.w4 = nullptr;
     if (L.wh && (L.CP == 128 || L.CP == 256)) {
-        // conv + BN + ReLU, conv + bias and the softmax of four boards per workgroup in one launch
-        Head4Args hd;
-        hd.x = x; hd.w = L.wh; hd.shift1 = shift(li); hd.bias2 = shift(li + 1); hd.policy = L.policy; hd.logits = L.want_logits ? L.logits : nullptr;
-        hd.flags = L.flags; hd.B = L.B;
-        hd.vw = L.vw; hd.vshift = L.vshift; hd.fcw = L.fcw; hd.fcb = L.fcb; hd.fc4 = L.fc4; hd.vfull = L.vfull;
-        li += 2;
+        // policy and value heads of four boards per workgroup in one launch          nn.cpp:72-88
+        const Head4Args hd = head_args(L, x, li);
         const int lds = 4 * CHUNKB + 4 * 64 * (128 * 2 + 16) + 4 * 64 * 4;
-        static std::atomic<bool> attr_done{ false };
-        if (!attr_done.load(std::memory_order_acquire)) {
-            if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&policy_head4_kernel<T, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-            if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&policy_head4_kernel<T, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)) != hipSuccess) return e;
-            attr_done.store(true, std::memory_order_release);
-        }
+        if ((e = allow_lds<&policy_head4_kernel<T, 1>>()) != hipSuccess) return e;
+        if ((e = allow_lds<&policy_head4_kernel<T, 2>>()) != hipSuccess) return e;
         if (L.CP == 128) hipLaunchKernelGGL((policy_head4_kernel<T, 1>), dim3((L.B + 3) / 4), dim3(256), lds, s, hd);
         else hipLaunchKernelGGL((policy_head4_kernel<T, 2>), dim3((L.B + 3) / 4), dim3(256), lds, s, hd);
-        if ((e = hipGetLastError()) != hipSuccess) return e;
-    } else {
-    a.in = x; a.w = layer(li); a.shift = shift(li); a.skip = nullptr; a.out = L.pmid; a.Ci = L.CP; a.Co = KH_POLICY_MID; ++li;
+        return hipGetLastError();
+    }
+    // policy head                                                           nn.cpp:72-80
+    ConvArgs a;
+    a.B = L.B; a.w4 = nullptr; a.skip = nullptr;
+    a.in = x; a.w = L.w + L.w_off[li]; a.shift = L.shift + L.shift_off[li]; a.out = L.pmid; a.Ci = L.CP; a.Co = KH_POLICY_MID; ++li;
     if ((e = launch_conv<T, 1, 0>(a, s)) != hipSuccess) return e;
-    a.in = L.pmid; a.w = layer(li); a.shift = shift(li); a.out = L.logits; a.Ci = KH_POLICY_MID; a.Co = 128; ++li;
+    a.in = L.pmid; a.w = L.w + L.w_off[li]; a.shift = L.shift + L.shift_off[li]; a.out = L.logits; a.Ci = KH_POLICY_MID; a.Co = 128;
     if ((e = launch_conv<T, 1, 2>(a, s)) != hipSuccess) return e;
     launch_softmax4672(L.logits, L.policy, L.B, L.flags, s);                  // nn.cpp:80
     // value head                                                            nn.cpp:83-88
-    int vb = (int)((npix + 255) / 256);
-    if (vb > 4096) vb = 4096;
+    const long npix = (long)L.B * 64;
+    const int vb = (int)std::min<long>((npix + 255) / 256, 4096);
     hipLaunchKernelGGL(value_conv_kernel<T>, dim3(vb), dim3(256), 0, s, x, L.vw, L.vshift, L.v64, npix, L.CP);
     launch_value_fc(L.v64, L.fcw, L.fcb, L.vfull, L.B, L.flags, s);
-    }
     return hipGetLastError();
 }
 
-}  // namespace lay
+template <typename T> static hipError_t run(const LayersArgs& L, hipStream_t s)
+{
+    const long npix = (long)L.B * 64;
+    auto planes_to_act = [&] {
+        const int blocks = (int)std::min<long>((npix * (L.FP / 8) + 255) / 256, 4096);
+        hipLaunchKernelGGL(planes_to_act_kernel<T>, dim3(blocks), dim3(256), 0, s, L.in, L.act_in, npix, L.F, L.FP);
+    };
+    auto layer4 = [&](size_t idx) -> const unsigned short* { return (L.w4 && L.w4_off[idx] != (size_t)-1) ? L.w4 + L.w4_off[idx] : nullptr; };
+    const unsigned magic = (unsigned)((0x100000000ull + L.F - 1) / L.F);
+    const size_t tower_layers = 1 + 2 * (size_t)L.R;
+    unsigned short* x = L.act[0];
+    hipError_t e;
+    switch (choose_plan(L)) {
+    case Plan::Tower128Fused: {
+        if ((e = allow_lds<&tower128_kernel<T, false>>()) != hipSuccess) return e;
+        if ((e = allow_lds<&tower128_kernel<T, true>>()) != hipSuccess) return e;
+        // the fp32 planes are read by the kernel itself when they allow 16-byte loads, converted beforehand otherwise
+        const bool direct = (reinterpret_cast<uintptr_t>(L.in) & 15) == 0;
+        if (!direct) planes_to_act();
+        Tower128Args t8;
+        t8.planes = direct ? L.in : nullptr; t8.F = L.F; t8.magic = magic;
+        t8.in = L.act_in; t8.w = layer4(0); t8.shift = L.shift + L.shift_off[0]; t8.out = x; t8.B = L.B; t8.R = L.R;
+        const int lds = 4 * CHUNKB + 4 * NPIX * (128 * 2 + 16);
+        if (L.wh) {              // both heads inside the same launch
+            t8.hd = head_args(L, nullptr, tower_layers);
+            hipLaunchKernelGGL((tower128_kernel<T, true>), dim3((L.B + 3) / 4), dim3(256), lds, s, t8);
+            return hipGetLastError();
+        }
+        hipLaunchKernelGGL((tower128_kernel<T, false>), dim3((L.B + 3) / 4), dim3(256), lds, s, t8);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        return run_heads<T>(L, x, tower_layers, s);
+    }
+    case Plan::Tower2b: {
+        if ((e = allow_lds<&tower2b_kernel<T, 256>>()) != hipSuccess) return e;
+        if ((e = allow_lds<&tower2b_kernel<T, 128>>()) != hipSuccess) return e;
+        Tower256Args t2;
+        t2.planes = L.in; t2.F = L.F; t2.magic = magic;
+        t2.w = L.CP == 256 ? L.w2b : layer4(0); t2.shift = L.shift + L.shift_off[0]; t2.out = x; t2.B = L.B; t2.R = L.R;
+        if (L.CP == 256) hipLaunchKernelGGL((tower2b_kernel<T, 256>), dim3((L.B + 1) / 2), dim3(256), 2 * NPIX * (256 * 2 + 16), s, t2);
+        else hipLaunchKernelGGL((tower2b_kernel<T, 128>), dim3((L.B + 1) / 2), dim3(256), 2 * NPIX * (128 * 2 + 16), s, t2);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        return run_heads<T>(L, x, tower_layers, s);
+    }
+    case Plan::Tower2s: {
+        if ((e = allow_lds<&tower2s_kernel<T>>()) != hipSuccess) return e;
+        const int pairs = (L.B + 1) / 2;
+        // every polled word zero before every launch (a block of its own at the allocation's start, a multiple of 16 bytes)
+        if ((e = hipMemsetAsync(L.xflag, 0, layers_xflag_bytes(pairs), s)) != hipSuccess) return e;
+        Tower2sArgs t2;
+        t2.planes = L.in; t2.F = L.F; t2.magic = magic;
+        t2.w = L.w2b; t2.shift = L.shift + L.shift_off[0]; t2.out = x; t2.B = L.B; t2.R = L.R;
+        t2.xbuf = L.xbuf; t2.xflag = L.xflag; t2.flags = L.flags; t2.npairs = pairs;
+        hipLaunchKernelGGL((tower2s_kernel<T>), dim3(tower2s_grid(L.B)), dim3(384), 2 * NPIX * (256 * 2 + 16), s, t2);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        return run_heads<T>(L, x, tower_layers, s);
+    }
+    case Plan::PerLayer: {
+        planes_to_act();
+        unsigned short *t = L.act[1], *u = L.act[2];
+        size_t li = 0;
+        ConvArgs a;
+        a.B = L.B;
+        // stem                                                                  nn.cpp:62-65
+        a.in = L.act_in; a.w = L.w + L.w_off[li]; a.w4 = layer4(li); a.shift = L.shift + L.shift_off[li]; a.skip = nullptr; a.out = x; a.Ci = L.FP; a.Co = L.CP; ++li;
+        if ((e = launch_conv<T, 9, 0>(a, s)) != hipSuccess) return e;
+        for (int r = 0; r < L.R; ++r) {                                       // nn.cpp:26-34
+            a.in = x; a.w = L.w + L.w_off[li]; a.w4 = layer4(li); a.shift = L.shift + L.shift_off[li]; a.skip = nullptr; a.out = t; a.Ci = L.CP; a.Co = L.CP; ++li;
+            if ((e = launch_conv<T, 9, 0>(a, s)) != hipSuccess) return e;
+            a.in = t; a.w = L.w + L.w_off[li]; a.w4 = layer4(li); a.shift = L.shift + L.shift_off[li]; a.skip = x; a.out = u; ++li;
+            if ((e = launch_conv<T, 9, 1>(a, s)) != hipSuccess) return e;
+            std::swap(x, u);
+        }
+        return run_heads<T>(L, x, li, s);
+    }
+    }
+    return hipErrorInvalidValue;
+}
 
-#ifdef KAMI_WIDE_DIAG
-extern "C" int kh_debug_t128_stamps(unsigned long long* out, int n)
-{
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(lay::g_t128_stamps), (size_t)n * 8, 0, hipMemcpyDeviceToHost);
-}
-extern "C" int kh_debug_t2s_stamps(unsigned long long* out, int n)
-{
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(lay::g_t2s_stamps), (size_t)n * 8, 0, hipMemcpyDeviceToHost);
-}
-extern "C" int kh_debug_wide_stamps(unsigned long long* out, int n)
-{
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(lay::g_wide_stamps), (size_t)n * 8, 0, hipMemcpyDeviceToHost);
-}
-#endif
+}  // namespace lay
 
 size_t layers_lds_bytes(int Ci) { return (size_t)lay::LDS_IMG + (size_t)2 * lay::NPIX * (Ci * 2 + 16); }
 

@@ -218,7 +218,7 @@ def test_wide_two_workgroups_per_cu_variant_matches(dtype, C, B, step):
     output channels; channels >= 128 sum their 64-channel slices in the order 2,3,0,1), larger ones tower2b_kernel
     (0,1,2,3): bit-identical within each range ((200, 50), (131, 50), (600, 300)), equal to rounding across the two
     ((515, 103): observed 1.2e-2 on logits / 7e-4 on probabilities / 7e-4 on values in f16 at TWENTY blocks, 8.9e-2 /
-    3.9e-3 / 4.8e-3 in bf16 — tools/split_check.py; both ranges are pinned against the oracle at full depth by
+    3.9e-3 / 4.8e-3 in bf16 — profiles/r03_tower2s_ab_stamps.txt; both ranges are pinned against the oracle at full depth by
     test_full_size_properties_wide_configs)."""
     F, R = 119, 2
     nn = NN(8, 8, F, 4672, filters=C, residuals=R, dtype=dtype)

@@ -161,7 +161,7 @@ for Cc, Rr, B, dt in ((128, 10, 1024, "bf16"), (256, 20, 256, "f16"), (256, 20, 
 if wide:
     json.dump({"round": rnd, "kernel_source_sha16": sha, "configs": wide}, open(f"{dst}/{tag}_wide_summary.json", "w"), indent=1)
 
-for name in ("wide_variants", "host_path_bench", "pinned_probe", "selfplay_bench", "train_bench", "train_bench_valu", "encode_bench"):
+for name in ("host_path_bench", "pinned_probe", "selfplay_bench", "train_bench", "train_bench_valu", "encode_bench"):
     p = f"{src}/{name}.txt"
     if os.path.exists(p) and os.path.getsize(p):
         shutil.copy(p, f"{dst}/{tag}_{name}.txt")

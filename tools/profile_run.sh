@@ -25,7 +25,6 @@ for cfg in "128 10 1024 bf16" "256 20 256 f16" "256 20 2048 f16"; do
   timeout -k 10 200 rocprofv3 --pmc $SQ --output-format csv -d $O/pmcs_$tag -- python3 tools/wide_profile.py $cfg 3 > $O/pmcs_$tag.log 2>&1 || { tail $O/pmcs_$tag.log; exit 1; }
   echo "wide $tag done"
 done
-timeout -k 10 300 python tools/wide_variants.py > $O/wide_variants.txt 2>&1
 timeout -k 10 200 python tools/host_path_bench.py > $O/host_path_bench.txt 2>&1
 timeout -k 10 200 python tools/pinned_probe.py > $O/pinned_probe.txt 2>&1
 timeout -k 10 300 python tools/selfplay_bench.py > $O/selfplay_bench.txt 2>&1
