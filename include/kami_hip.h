@@ -139,14 +139,34 @@ int  kh_train_order(int trajectories, int epochs, int32_t* order);
  * parameters in blob order (BatchNorm num_batches_tracked counters are not part of the blob).  No GPU needed. */
 int  kh_checkpoint_read(const char* path, int* features, int* filters, int* residuals, int* generation,
                         float* blob, size_t cap, size_t* nfloats);
-/* NN::read as a whole: kh_checkpoint_read + shape check against cfg + kh_load_weights. */
+/* kh_checkpoint_read, and also the BatchNorm num_batches_tracked counter of a libtorch archive (the first layer's:
+ * kami's layers all hold one value) in *bn_batches when non-NULL; 0 for a KAMW blob or an archive without counters. */
+int  kh_checkpoint_read_ex(const char* path, int* features, int* filters, int* residuals, int* generation,
+                           int64_t* bn_batches, float* blob, size_t cap, size_t* nfloats);
+/* NN::read as a whole: kh_checkpoint_read + shape check against cfg + kh_load_weights.  The engine's BatchNorm
+ * batch counter (kh_bn_batches) takes the archive's value. */
 int  kh_load_checkpoint(kh_engine* e, const char* path);
+
+/* NN::write (nn.cpp:189-202) in the reference's own format: a libtorch archive (uncompressed zip, no zip64) that the
+ * reference's NN::read and torch.jit.load open, holding the blob's tensors under the reference's names, every
+ * BatchNorm's num_batches_tracked = bn_batches (int64) and `generation`.  Written to a temporary file next to `path`
+ * and renamed into place: a failed write leaves no file.  KH_ERR_INVALID for a bad shape, a blob of the wrong size,
+ * an archive that would need zip64, or an I/O failure.  No engine and no GPU needed. */
+int  kh_checkpoint_write(const char* path, int features, int filters, int residuals, int generation, int64_t bn_batches,
+                         const float* blob, size_t nfloats);
+/* kh_get_weights + kh_generation + kh_bn_batches + kh_checkpoint_write, all of one installed parameter set. */
+int  kh_write_checkpoint(kh_engine* e, const char* path);
 
 /* The engine's current fp32 parameter set in blob order (what NN::write would serialise, nn.cpp:189-202). */
 int  kh_get_weights(kh_engine* e, float* blob, size_t nfloats);
 
 /* NN::get_generation nn.h:53-59. */
 int  kh_generation(kh_engine* e);
+
+/* The reference's BatchNorm num_batches_tracked for the installed parameters: set from a libtorch archive by
+ * kh_load_checkpoint, 0 after kh_load_weights or a KAMW read, + epochs * ceil(trajectories / batch) per kh_train
+ * (one per training-mode forward), copied by kh_clone.  It enters no computation; kh_write_checkpoint writes it. */
+int  kh_bn_batches(kh_engine* e, int64_t* count);
 
 /* NN(NN* other) nn.cpp:130-153: a new engine with the same config and weights. */
 int  kh_clone(kh_engine* src, kh_engine** out);

@@ -45,7 +45,12 @@ SYMBOLS = {
     "kh_train_order": (C.c_int, [C.c_int, C.c_int, _P]),
     "kh_checkpoint_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                      _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "kh_checkpoint_read_ex": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
+                                        C.POINTER(C.c_int64), _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "kh_load_checkpoint": (C.c_int, [_P, C.c_char_p]),
+    "kh_checkpoint_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, _P, C.c_size_t]),
+    "kh_write_checkpoint": (C.c_int, [_P, C.c_char_p]),
+    "kh_bn_batches": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "kh_get_weights": (C.c_int, [_P, _P, C.c_size_t]),
     "kh_generation": (C.c_int, [_P]),
     "kh_clone": (C.c_int, [_P, C.POINTER(_P)]),

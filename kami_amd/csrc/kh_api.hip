@@ -6,6 +6,7 @@
 // without a gfx950 device kh_create fails with KH_ERR_NO_DEVICE.
 #include "kh_internal.h"
 #include "torch_archive.h"
+#include "torch_archive_write.h"
 
 #include <sched.h>
 #include <atomic>
@@ -118,6 +119,7 @@ HostNet parse_blob(const float* blob, int F, int C, int R)
 // the engine's shared_ptr; calls in flight keep the old set alive until they finish.
 struct Weights {
     int generation = 0;
+    int64_t bn_batches = 0;              // BatchNorm num_batches_tracked of the reference (kh_bn_batches): carried, never computed with
     std::vector<float> blob;             // host copy (kh_clone)
     DevMem simple;                       // fp32 [tap][ci][co] + scale/shift per layer
     std::vector<kh::SimpleLayer> layers; // stem, 2R tower convs, policyconv, policyconv2, valueconv
@@ -1652,7 +1654,8 @@ void kh_destroy(kh_engine* e)
     delete e;
 }
 
-static int load_weights_impl(kh_engine* e, const float* blob, size_t nfloats, int generation, std::shared_ptr<Weights>* installed)
+static int load_weights_impl(kh_engine* e, const float* blob, size_t nfloats, int generation, int64_t bn_batches,
+                             std::shared_ptr<Weights>* installed)
 {
     if (!e || !blob) return fail(KH_ERR_INVALID, "null argument");
     const int F = e->cfg.features, C = e->cfg.filters, R = e->cfg.residuals;
@@ -1663,6 +1666,7 @@ static int load_weights_impl(kh_engine* e, const float* blob, size_t nfloats, in
     if (rc) return rc;
     auto W = std::make_shared<Weights>();
     W->generation = generation;
+    W->bn_batches = bn_batches;
     W->blob.assign(blob, blob + nfloats);
     HostNet n = parse_blob(W->blob.data(), F, C, R);
     if (e->cfg.dtype == KH_F32) {
@@ -1681,7 +1685,7 @@ static int load_weights_impl(kh_engine* e, const float* blob, size_t nfloats, in
 
 int kh_load_weights(kh_engine* e, const float* blob, size_t nfloats, int generation)
 {
-    return load_weights_impl(e, blob, nfloats, generation, nullptr);
+    return load_weights_impl(e, blob, nfloats, generation, 0, nullptr);
 }
 
 int kh_train(kh_engine* e, const float* inputs, const float* obs_p, const float* obs_v, int trajectories,
@@ -1809,7 +1813,10 @@ int kh_train(kh_engine* e, const float* inputs, const float* obs_p, const float*
     if (last_loss) *last_loss = lastloss;
     const auto t_read = std::chrono::steady_clock::now();
     std::shared_ptr<Weights> installed;
-    const int lrc = load_weights_impl(e, blob.data(), nfl, W->generation + 1, &installed);         // nn.cpp:371 ++generation
+    // every training-mode forward (one per batch, the short last one included: nn.cpp:264-301) counts once in each
+    // BatchNorm's num_batches_tracked
+    const int64_t forwards = (int64_t)cfg->epochs * ((trajectories + B - 1) / B);
+    const int lrc = load_weights_impl(e, blob.data(), nfl, W->generation + 1, W->bn_batches + forwards, &installed);  // nn.cpp:371 ++generation
     if (lrc == KH_OK) tc.on_device = installed;
     if (trace) {
         auto ms = [](std::chrono::steady_clock::duration d) { return std::chrono::duration<double, std::milli>(d).count(); };
@@ -1836,12 +1843,19 @@ int kh_train_order(int trajectories, int epochs, int32_t* order)
 int kh_checkpoint_read(const char* path, int* features, int* filters, int* residuals, int* generation,
                        float* blob, size_t cap, size_t* nfloats)
 {
+    return kh_checkpoint_read_ex(path, features, filters, residuals, generation, nullptr, blob, cap, nfloats);
+}
+
+int kh_checkpoint_read_ex(const char* path, int* features, int* filters, int* residuals, int* generation, int64_t* bn_batches,
+                          float* blob, size_t cap, size_t* nfloats)
+{
     if (!path) return fail(KH_ERR_INVALID, "null path");
     FILE* f = fopen(path, "rb");
     if (!f) return fail(KH_ERR_INVALID, "cannot open %s", path);
     int32_t hdr[8] = { 0 };
     const size_t got = fread(hdr, 1, sizeof hdr, f);
     int F = 0, C = 0, R = 0, gen = 0;
+    int64_t nbt = 0;                     // KAMW carries no counter
     std::vector<float> data;
     if (got == sizeof hdr && hdr[0] == 0x574d414b /* "KAMW" */) {
         F = hdr[1]; C = hdr[2]; R = hdr[3]; gen = hdr[4];
@@ -1872,6 +1886,7 @@ int kh_checkpoint_read(const char* path, int* features, int* filters, int* resid
             if (f64 < 1 || f64 > 4096 || c64 < 1 || c64 > 1024) return fail(KH_ERR_INVALID, "%s: conv1.weight has an impossible shape", path);
             if (g->second < INT32_MIN || g->second > INT32_MAX) return fail(KH_ERR_INVALID, "%s: generation out of range", path);
             C = (int)c64; F = (int)f64; gen = (int)g->second;
+            nbt = ck.bn_batches;
             while (R <= 256 && ck.tensors.count("residual" + std::to_string(R) + ".conv1.weight")) ++R;
             if (R > 256) return fail(KH_ERR_INVALID, "%s: more than 256 residual blocks", path);
             // blob order of kh_weight_count (names per nn.cpp:20-23,45-56)
@@ -1908,6 +1923,7 @@ int kh_checkpoint_read(const char* path, int* features, int* filters, int* resid
     if (filters) *filters = C;
     if (residuals) *residuals = R;
     if (generation) *generation = gen;
+    if (bn_batches) *bn_batches = nbt;
     if (nfloats) *nfloats = data.size();
     if (blob) {
         if (cap < data.size()) return fail(KH_ERR_INVALID, "blob buffer holds %zu floats, the checkpoint has %zu", cap, data.size());
@@ -1920,15 +1936,44 @@ int kh_load_checkpoint(kh_engine* e, const char* path)
 {
     if (!e) return fail(KH_ERR_INVALID, "null engine");
     int F, C, R, gen;
+    int64_t nbt = 0;
     size_t n = 0;
-    int rc = kh_checkpoint_read(path, &F, &C, &R, &gen, nullptr, 0, &n);
+    int rc = kh_checkpoint_read_ex(path, &F, &C, &R, &gen, &nbt, nullptr, 0, &n);
     if (rc) return rc;
     if (F != e->cfg.features || C != e->cfg.filters || R != e->cfg.residuals)
         return fail(KH_ERR_INVALID, "%s holds a %d-plane %dx%d network, this engine is %d-plane %dx%d", path, F, R, C,
                     e->cfg.features, e->cfg.residuals, e->cfg.filters);
     std::vector<float> blob(n);
     if ((rc = kh_checkpoint_read(path, nullptr, nullptr, nullptr, nullptr, blob.data(), blob.size(), nullptr))) return rc;
-    return kh_load_weights(e, blob.data(), blob.size(), gen);
+    return load_weights_impl(e, blob.data(), blob.size(), gen, nbt, nullptr);
+}
+
+int kh_checkpoint_write(const char* path, int features, int filters, int residuals, int generation, int64_t bn_batches,
+                        const float* blob, size_t nfloats)
+{
+    if (!path || !blob) return fail(KH_ERR_INVALID, "null argument");
+    if (features < 1 || features > 4096 || filters < 1 || filters > 1024 || residuals < 0 || residuals > 256)
+        return fail(KH_ERR_INVALID, "impossible network shape F=%d C=%d R=%d", features, filters, residuals);
+    if (nfloats != kh_weight_count(features, filters, residuals))
+        return fail(KH_ERR_INVALID, "weight blob has %zu floats, expected %zu for F=%d C=%d R=%d", nfloats,
+                    kh_weight_count(features, filters, residuals), features, filters, residuals);
+    if (bn_batches < 0) return fail(KH_ERR_INVALID, "negative BatchNorm batch count");
+    try {
+        kh_archive::write_checkpoint(path, features, filters, residuals, generation, bn_batches, blob, nfloats,
+                                     KH_POLICY_MID, KH_POLICY_PLANES, KH_VALUE_WIDTH);
+    } catch (const std::exception& ex) {
+        return fail(KH_ERR_INVALID, "%s: %s", path, ex.what());
+    }
+    return KH_OK;
+}
+
+int kh_write_checkpoint(kh_engine* e, const char* path)
+{
+    if (!e || !path) return fail(KH_ERR_INVALID, "null argument");
+    auto W = current_weights(e);                 // one parameter set: blob, generation and counter belong together
+    if (!W) return fail(KH_ERR_NO_WEIGHTS, "no weights loaded");
+    return kh_checkpoint_write(path, e->cfg.features, e->cfg.filters, e->cfg.residuals, W->generation, W->bn_batches,
+                               W->blob.data(), W->blob.size());
 }
 
 int kh_get_weights(kh_engine* e, float* blob, size_t nfloats)
@@ -1948,13 +1993,21 @@ int kh_generation(kh_engine* e)
     return W ? W->generation : 0;
 }
 
+int kh_bn_batches(kh_engine* e, int64_t* count)
+{
+    if (!e || !count) return fail(KH_ERR_INVALID, "null argument");
+    auto W = current_weights(e);
+    *count = W ? W->bn_batches : 0;
+    return KH_OK;
+}
+
 int kh_clone(kh_engine* src, kh_engine** out)
 {
     if (!src || !out) return fail(KH_ERR_INVALID, "null argument");
     int rc = kh_create(&src->cfg, out);
     if (rc) return rc;
     auto W = current_weights(src);
-    if (W && (rc = kh_load_weights(*out, W->blob.data(), W->blob.size(), W->generation))) {
+    if (W && (rc = load_weights_impl(*out, W->blob.data(), W->blob.size(), W->generation, W->bn_batches, nullptr))) {
         kh_destroy(*out);
         *out = nullptr;
         return rc;

@@ -26,6 +26,8 @@ struct Tensor {
 struct Checkpoint {
     std::map<std::string, Tensor> tensors;     // dotted names: "residual0.conv1.weight"
     std::map<std::string, int64_t> ints;       // top-level integer attributes: "generation"
+    int64_t bn_batches = 0;                    // the first BatchNorm's num_batches_tracked (kami's layers share one value)
+    bool has_bn_batches = false;
 };
 
 namespace detail {
@@ -279,7 +281,15 @@ inline Checkpoint read_checkpoint(const std::string& path)
                 const Value& v = *kv.second;
                 if (v.kind == Value::OBJECT) walk(v, name + ".", depth + 1);
                 else if (v.kind == Value::TENSOR) {
-                    if (name.size() > 19 && name.compare(name.size() - 19, 19, "num_batches_tracked") == 0) continue;   // int64 counters nn.cpp never reads
+                    if (name.size() > 19 && name.compare(name.size() - 19, 19, "num_batches_tracked") == 0) {
+                        // int64 counters nn.cpp never reads: kept as one number (the first), never part of the blob
+                        if (ck.has_bn_batches || v.s != "LongStorage" || !v.size.empty() || v.offset < 0) continue;
+                        auto it = members.find(root + "/data/" + v.s2);
+                        if (it == members.end() || it->second.method != 0 || (uint64_t)v.offset >= it->second.size / 8) continue;
+                        memcpy(&ck.bn_batches, &z[it->second.offset + (size_t)v.offset * 8], 8);
+                        ck.has_bn_batches = true;
+                        continue;
+                    }
                     if (v.s != "FloatStorage") bad(name + " is not an fp32 tensor");
                     auto it = members.find(root + "/data/" + v.s2);
                     if (it == members.end()) bad("storage " + v.s2 + " missing");

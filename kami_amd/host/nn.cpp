@@ -201,8 +201,18 @@ void NN::train(int trajectories, float* inputs, float* obs_p, float* obs_v, bool
               << cfg.epochs << " epochs\n";                      // nn.cpp:372
 }
 
+// nn.cpp:189-202.  Option "model_format": "torch" writes the reference's own libtorch archive (kh_write_checkpoint),
+// which a stock kami's NN::read loads; absent or "kamw", the engine's KAMW container.
 void NN::write(std::string path)
 {
+    const std::string format = options::getStr("model_format", "kamw");
+    if (format == "torch") {
+        int rc = kh_write_checkpoint(eng, path.c_str());
+        if (rc) raise(rc);
+        std::cout << "Saved model to " << path << std::endl;      // nn.cpp:201
+        return;
+    }
+    if (format != "kamw") throw std::runtime_error("model_format must be kamw or torch, not " + format);
     std::vector<float> blob;
     {
         std::lock_guard<std::mutex> lk(g_store_mu);
@@ -218,7 +228,7 @@ void NN::write(std::string path)
 
 // nn.cpp:204-222.  Reads what the reference's NN::write leaves on disk — a libtorch archive (module.save +
 // the "generation" IValue), parsed by the engine without libtorch (kh_checkpoint_read) — as well as the
-// engine's own KAMW container that write() above produces.
+// engine's own KAMW container that write() above produces.  An archive's BatchNorm batch counter comes along.
 void NN::read(std::string path)
 {
     int F = 0, C = 0, R = 0, gen = 0;
@@ -227,9 +237,11 @@ void NN::read(std::string path)
     if (rc) raise(rc);
     if (F != features || C != filters || R != residuals)
         throw std::runtime_error(path + ": network shape does not match this NN");
+    if ((rc = kh_load_checkpoint(eng, path.c_str()))) raise(rc);
     std::vector<float> blob(n);
-    if ((rc = kh_checkpoint_read(path.c_str(), nullptr, nullptr, nullptr, nullptr, blob.data(), blob.size(), nullptr))) raise(rc);
-    load_blob(blob.data(), blob.size(), gen);
+    if ((rc = kh_get_weights(eng, blob.data(), blob.size()))) raise(rc);
+    std::lock_guard<std::mutex> lk(g_store_mu);
+    g_store[this] = std::move(blob);
 }
 
 NN* NN::clone() { return new NN(this); }

@@ -50,6 +50,25 @@ def read_checkpoint(path: str):
     return blob, F.value, Cc.value, R.value, gen.value
 
 
+def read_bn_batches(path: str) -> int:
+    """The BatchNorm num_batches_tracked counter a checkpoint holds (kh_checkpoint_read_ex): the first layer's for a
+    libtorch archive, 0 for a KAMW blob.  Needs no GPU."""
+    lib = L.load()
+    nbt, n = C.c_int64(), C.c_size_t()
+    _chk(lib.kh_checkpoint_read_ex(path.encode(), None, None, None, None, C.byref(nbt), None, 0, C.byref(n)))
+    return nbt.value
+
+
+def write_checkpoint(path: str, blob: np.ndarray, features: int, filters: int, residuals: int, generation: int,
+                     bn_batches: int = 0) -> None:
+    """kh_checkpoint_write: the blob as the reference's own checkpoint format (a libtorch archive that kami's
+    NN::read, nn.cpp:204-222, and torch.jit.load open), every BatchNorm's num_batches_tracked = bn_batches.
+    The file appears only once complete.  Needs no GPU."""
+    lib = L.load()
+    b = np.ascontiguousarray(blob, dtype=np.float32)
+    _chk(lib.kh_checkpoint_write(path.encode(), features, filters, residuals, generation, bn_batches, _ptr(b), b.size))
+
+
 class Ticket:
     """An outstanding kh_submit_*: keeps the caller-side buffers alive until wait() (the engine reads and writes them)."""
 
@@ -160,16 +179,30 @@ class NN:
         return policy, value
 
     def read(self, path: str) -> None:
-        """NN::read (nn.cpp:204-222): the reference's own libtorch archives and the engine's KAMW blobs."""
+        """NN::read (nn.cpp:204-222): the reference's own libtorch archives and the engine's KAMW blobs.  An archive's
+        BatchNorm batch counter comes along (bn_batches())."""
         blob, F, Cc, R, gen = read_checkpoint(path)
         if (F, Cc, R) != (self.cfg.features, self.cfg.filters, self.cfg.residuals):
             raise KamiError(L.KH_ERR_INVALID, "checkpoint shape does not match this NN")
-        self.load_weights(blob, gen)
+        _chk(self._lib.kh_load_checkpoint(self._h, path.encode()))
+        self._blob = blob
 
-    def write(self, path: str) -> None:
-        """NN::write (nn.cpp:189-202) into the engine's KAMW container (read() takes it back, and the reference's own
-        archives as well)."""
-        W.save(path, self.get_weights(), self.cfg.features, self.cfg.filters, self.cfg.residuals, self.get_generation())
+    def write(self, path: str, format: str = "kamw") -> None:
+        """NN::write (nn.cpp:189-202).  format="kamw" (the default): the engine's KAMW container; format="torch": the
+        reference's own libtorch archive (kh_write_checkpoint), which a stock kami reads.  read() takes both back."""
+        if format == "torch":
+            _chk(self._lib.kh_write_checkpoint(self._h, path.encode()))
+        elif format == "kamw":
+            W.save(path, self.get_weights(), self.cfg.features, self.cfg.filters, self.cfg.residuals, self.get_generation())
+        else:
+            raise ValueError(f"format must be 'kamw' or 'torch', not {format!r}")
+
+    def bn_batches(self) -> int:
+        """kh_bn_batches: the reference's BatchNorm num_batches_tracked for the current weights (training-mode forwards
+        so far; from the archive after read(), 0 after load_weights())."""
+        v = C.c_int64()
+        _chk(self._lib.kh_bn_batches(self._h, C.byref(v)))
+        return v.value
 
     def clone(self) -> "NN":
         other = object.__new__(NN)
