@@ -1,5 +1,5 @@
 // encode_square.h — Env::observe (kami/env.h:202-262) for ONE point-of-view square, shared by the
-// stand-alone encode kernel (encode.hip) and the fused ingest of the tower kernel (tower_mfma.hip).
+// stand-alone encode kernel (encode.hip) and the fused ingest of the whole-network kernel (tower8_mfma.hip).
 #pragma once
 #include "../../include/kami_hip.h"
 

@@ -124,8 +124,8 @@ struct Weights {
     DevMem simple;                       // fp32 [tap][ci][co] + scale/shift per layer
     std::vector<kh::SimpleLayer> layers; // stem, 2R tower convs, policyconv, policyconv2, valueconv
     const float *fcw = nullptr, *fcb = nullptr;
-    // whole-network MFMA kernel (tower_mfma.hip): packed fragment stream + folded parameters
-    DevMem tw_stream, tw_stream8, tw_par, tw_fc4;      // tw_stream8: the stream in tower8_kernel's stem order (empty: same as tw_stream)
+    // whole-network MFMA kernel (tower8_mfma.hip): packed fragment stream + folded parameters
+    DevMem tw_stream, tw_par, tw_fc4;
     int tw_nchunks = 0, tw_npar = 0, tw_FP = 0;
     bool tw_ok = false;
     std::string tw_why;
@@ -172,9 +172,9 @@ uint16_t f2f16(float f)
 // Append one layer's MFMA A-operand fragments (v_mfma_f32_32x32x16: lane l = (r = l & 31, h = l >> 5)
 // holds W[co = ms*32 + r][k = 8h + j], j = 0..7) in consumption order tap -> k-step -> ms, BN scale
 // folded in before rounding, zero-padded to (MS*32, KS*16) and to a whole number of 8-fragment chunks.
-// ci0: first input channel of this pass (the 128-plane stem runs as two 64-channel passes).
+// ci0: first input channel of this pass (the 33..128-plane stem runs as four 32-channel passes).
 // centre_first: 3x3 taps in the order 4,0,1,2,3,5,6,7,8.  perm: the first `perm` k-steps of the
-// stream take their activations from the consumer's packed output registers (tower_mfma.hip,
+// stream take their activations from the consumer's packed output registers (tower_common.h,
 // packed_fragments): slot (h, j) of k-step ks is input channel
 // 32 (ks >> 1) + 8 (2 (ks & 1) + (j >> 2)) + 4 h + (j & 3) instead of 16 ks + 8 h + j.
 void pack_layer(std::vector<uint16_t>& out, int dtype, const float* w, const float* scale, int Co, int Ci,
@@ -382,14 +382,13 @@ int build_tower(Weights& W, const HostNet& n, int dtype, int F, int C, int R)
     const int FP = F <= 32 ? 32 : 128;
     if (tower_lds_bytes(FP, R) > 160 * 1024) { W.tw_why = "too many residual blocks for the LDS parameter area"; return KH_OK; }
     std::vector<float> sc(128), sh(128);
-    std::vector<uint16_t> stream, stem8;
+    std::vector<uint16_t> stream;
     std::vector<float> par((size_t)tower_par_copy_floats(R), 0.0f);
     fold_bn(n.stem, C, sc.data(), sh.data());
-    if (FP == 128) {        // two 64-plane passes: the second half of the planes is still arriving during the first
-        pack_layer(stream, dtype, n.stem.w, sc.data(), C, F, 9, 4, 2, 0);
-        pack_layer(stream, dtype, n.stem.w, sc.data(), C, F, 9, 4, 2, 64);
-        // tower8_kernel: four 32-plane passes in one unpadded run of 72 k-steps = the same 18 chunks
-        for (int q = 0; q < 4; ++q) pack_layer(stem8, dtype, n.stem.w, sc.data(), C, F, 9, 2, 2, 32 * q, false, 0, false);
+    if (FP == 128) {        // four 32-plane passes in one unpadded run of 72 k-steps: the later quarters of the planes are
+                            // still being converted while the first passes run
+        for (int q = 0; q < 4; ++q) pack_layer(stream, dtype, n.stem.w, sc.data(), C, F, 9, 2, 2, 32 * q, false, 0, false);
+        if (stream.size() != (size_t)18 * 4096) return fail(KH_ERR_INVALID, "internal: stem stream size");
     } else {
         pack_layer(stream, dtype, n.stem.w, sc.data(), C, F, 9, FP / 16, 2);
     }
@@ -405,7 +404,7 @@ int build_tower(Weights& W, const HostNet& n, int dtype, int F, int C, int R)
     float* pbias2 = pshift1 + KH_POLICY_MID;
     memcpy(pbias2, n.p2b, sizeof(float) * KH_POLICY_PLANES);
     pack_layer(stream, dtype, n.p2w, nullptr, KH_POLICY_PLANES, KH_POLICY_MID, 1, KH_POLICY_MID / 16, 4, 0, false, KH_POLICY_MID / 16);
-    if (((stream.size() / 4096) & 1) != 0) stream.resize(stream.size() + 4096, 0);   // parity chunk (see gemm_dummy)
+    if (((stream.size() / 4096) & 1) != 0) stream.resize(stream.size() + 4096, 0);   // parity chunk (see gemm8_dummy)
     float* vw = pbias2 + 128;
     float vs, vsh;
     fold_bn(n.vconv, 1, &vs, &vsh);
@@ -426,12 +425,6 @@ int build_tower(Weights& W, const HostNet& n, int dtype, int F, int C, int R)
     rc |= W.tw_fc4.ensure(fc4.size() * 4);
     if (rc) return KH_ERR_HIP;
     HIPCHK(hipMemcpy(W.tw_stream.p, stream.data(), stream.size() * 2, hipMemcpyHostToDevice));
-    if (!stem8.empty()) {
-        if (stem8.size() != (size_t)18 * 4096 || stem8.size() > stream.size()) return fail(KH_ERR_INVALID, "internal: stem stream size");
-        memcpy(stream.data(), stem8.data(), stem8.size() * 2);          // everything behind the stem is the same
-        if (W.tw_stream8.ensure(stream.size() * 2)) return KH_ERR_HIP;
-        HIPCHK(hipMemcpy(W.tw_stream8.p, stream.data(), stream.size() * 2, hipMemcpyHostToDevice));
-    }
     HIPCHK(hipMemcpy(W.tw_par.p, par.data(), par.size() * 4, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(W.tw_fc4.p, fc4.data(), fc4.size() * 4, hipMemcpyHostToDevice));
     W.tw_ok = true;
@@ -647,13 +640,18 @@ int forward_simple(kh_engine* e, const Weights& W, Slot& s, const float* d_in, i
     return KH_OK;
 }
 
-// The throughput path: one persistent kernel for the whole forward pass (tower_mfma.hip).
+// The throughput path: one persistent kernel for the whole forward pass (tower_mfma.hip, tower8_mfma.hip).
 struct LegalDev { const int32_t* offsets; const int32_t* actions; float* priors; float* values; int* flags; };
 
-// the weight stream in the running tower kernel's stem order (kh_internal.h: tower_variant)
-static const char* tower_stream(const Weights& W)
+// the kernel's arguments for B boards of fp32 planes at d_in; outputs, flags and legal-move mode are the caller's to set
+static kh::TowerArgs tower_args(const kh_engine* e, const Weights& W, const float* d_in, int B)
 {
-    return kh::tower_variant() == 8 && W.tw_stream8.p ? W.tw_stream8.as<char>() : W.tw_stream.as<char>();
+    kh::TowerArgs a;
+    a.in = d_in; a.boards = nullptr; a.B = B; a.F = e->cfg.features; a.R = e->cfg.residuals;
+    a.wstream = W.tw_stream.as<char>(); a.nchunks = W.tw_nchunks;
+    a.params = W.tw_par.as<float>(); a.npar = W.tw_npar;
+    a.fcw4 = W.tw_fc4.as<float>(); a.fcb = W.tw_fc4.as<float>() + (size_t)KH_VALUE_WIDTH * 64;
+    return a;
 }
 
 int forward_tower(kh_engine* e, const Weights& W, Slot& s, const float* d_in, int B,
@@ -668,11 +666,8 @@ int forward_tower(kh_engine* e, const Weights& W, Slot& s, const float* d_in, in
         HIPCHK(hipMemsetAsync(flags, 0, 16, st));   // not per launch (a memset node costs a launch boundary)
         s.flags_clean = true;
     }
-    kh::TowerArgs a;
-    a.in = d_in; a.boards = d_boards; a.B = B; a.F = e->cfg.features; a.R = e->cfg.residuals;
-    a.wstream = tower_stream(W); a.nchunks = W.tw_nchunks;
-    a.params = W.tw_par.as<float>(); a.npar = W.tw_npar;
-    a.fcw4 = W.tw_fc4.as<float>(); a.fcb = W.tw_fc4.as<float>() + (size_t)KH_VALUE_WIDTH * 64;
+    kh::TowerArgs a = tower_args(e, W, d_in, B);
+    a.boards = d_boards;
     a.policy = d_policy; a.vfull = d_vfull; a.logits = d_logits_out; a.flags = flags;
     if (lg) { a.lg_offsets = lg->offsets; a.lg_actions = lg->actions; a.lg_priors = lg->priors; a.lg_values = lg->values; a.lg_flags = lg->flags; }
     HIPCHK(kh::launch_tower(e->cfg.dtype, W.tw_FP, a, e->num_cus, st));
@@ -805,11 +800,7 @@ int infer_host_pinned(kh_engine* e, const Weights& W, Slot& s, const float* inpu
         const int n = std::min(per, batch - lo);
         hipStream_t q = st[k & 1];
         HIPCHK(hipMemcpyAsync(d_in + (size_t)lo * 64 * F, input + (size_t)lo * 64 * F, (size_t)n * 64 * F * 4, hipMemcpyHostToDevice, q));
-        kh::TowerArgs a;
-        a.in = d_in + (size_t)lo * 64 * F; a.boards = nullptr; a.B = n; a.F = e->cfg.features; a.R = e->cfg.residuals;
-        a.wstream = tower_stream(W); a.nchunks = W.tw_nchunks;
-        a.params = W.tw_par.as<float>(); a.npar = W.tw_npar;
-        a.fcw4 = W.tw_fc4.as<float>(); a.fcb = W.tw_fc4.as<float>() + (size_t)KH_VALUE_WIDTH * 64;
+        kh::TowerArgs a = tower_args(e, W, d_in + (size_t)lo * 64 * F, n);
         a.policy = d_pol + (size_t)lo * KH_PSIZE; a.vfull = d_vf + (size_t)lo * KH_VALUE_WIDTH; a.logits = nullptr; a.flags = flags;
         HIPCHK(kh::launch_tower(e->cfg.dtype, W.tw_FP, a, e->num_cus, q));
         HIPCHK(hipMemcpyAsync(policy + (size_t)lo * KH_PSIZE, d_pol + (size_t)lo * KH_PSIZE, (size_t)n * KH_PSIZE * 4, hipMemcpyDeviceToHost, q));
@@ -908,7 +899,7 @@ int infer_host(kh_engine* e, const float* input, const kh_board* boards, int bat
         memcpy(s.hin.at(in_acts), legal->actions, (size_t)nact * 4);
         if (fused && e->cfg.value_mode == KH_VALUE_PER_SAMPLE0) {
             // ONE launch, no copy engine: the kernel reads records / offsets / actions from the page-locked block and writes
-            // the legal priors, the values (column 0) and the NaN flags into the other one itself (tower_kernel's
+            // the legal priors, the values (column 0) and the NaN flags into the other one itself (tower8_kernel's
             // legal-move mode; what the queue's launches do); completion is polled
             int* fl = reinterpret_cast<int*>(s.hout.at(out_flags));
             fl[0] = fl[1] = 0;

@@ -40,8 +40,8 @@ void launch_softmax4672(const float* logits, float* policy, int B, int* flags, h
 void launch_value_fc(const float* v64, const float* fcw, const float* fcb, float* value_full,
                      int B, int* flags, hipStream_t s);
 
-// ---- tower_mfma.hip ---------------------------------------------------------------------
-// Whole-network persistent MFMA kernel (bf16 / f16 operands, fp32 accumulate).
+// ---- tower_mfma.hip, tower8_mfma.hip ---------------------------------------------------------
+// Whole-network persistent MFMA kernel (bf16 / f16 operands, fp32 accumulate) for nets of up to 64 filters.
 constexpr int TW_NB = 2;     // boards per workgroup pass
 constexpr int TW_CP = 64;    // channel count the kernel is specialised for (smaller nets are zero-padded)
 
@@ -49,7 +49,7 @@ struct TowerArgs {
     const float* in;         // [B][8][8][F] fp32 planes (ignored when boards != nullptr)
     const kh_board* boards;  // nullable: compact ingest, Env::observe fused into the kernel (F must be 30)
     int B, F, R;
-    const char* wstream;     // packed weight fragments, nchunks x 8 KB (see pack_tower in kh_api.hip)
+    const char* wstream;     // packed weight fragments, nchunks x 8 KB (see build_tower in kh_api.hip)
     int nchunks;
     const float* params;     // folded shifts / value-conv weights, npar floats
     int npar;
@@ -73,14 +73,10 @@ struct TowerArgs {
 // floats of LDS parameter area: shifts of the 1+2R 3x3 layers, policy shifts/bias, value conv, scratch
 __host__ __device__ constexpr int tower_par_copy_floats(int R) { return (1 + 2 * R) * TW_CP + 128 + 128 + TW_CP + 4; }
 __host__ __device__ constexpr int tower_par_floats(int R) { return tower_par_copy_floats(R) + TW_NB * 64 + 16; }
-int tower_lds_bytes(int FP, int R);
+int tower_lds_bytes(int FP, int R);      // tower_mfma.hip: dynamic LDS of one workgroup
+// tower8_mfma.hip: tower8_kernel, 4 compute + 4 helper waves per workgroup, one workgroup per CU.  FP: input planes padded
+// to 32 (F <= 32) or 128 (F <= 128); the weight stream walks a 33..128-plane stem as four passes of 32 planes.
 hipError_t launch_tower(int dtype, int FP, const TowerArgs& a, int num_cus, hipStream_t s);
-// tower8_mfma.hip: the same forward with specialised waves (4 compute + 4 helper waves per workgroup); launch_tower
-// dispatches to it (KAMI_TOWER_V=4|8 overrides the build's default for A/B runs)
-hipError_t launch_tower8(int dtype, int FP, const TowerArgs& a, int num_cus, hipStream_t s);
-// 4 or 8: which of the two launch_tower runs.  They walk a 33..128-plane stem in different orders (two passes of 64
-// planes / four of 32), so TowerArgs::wstream must be the stream packed for the running one.
-int tower_variant();
 
 // ---- layers_mfma.hip ----------------------------------------------------------------------
 // bf16 / f16 path for wide nets (65..256 filters): one MFMA kernel launch per layer.

@@ -1,5 +1,5 @@
 // layers_mfma.hip — bf16 / f16 forward pass for WIDE nets (65..256 filters) and the exact-fp32 path, on the matrix
-// cores.  The whole-network kernel (tower_mfma.hip) is specialised for <= 64 filters; from 128 filters up a 3x3 layer is
+// cores.  The whole-network kernel (tower8_mfma.hip) is specialised for <= 64 filters; from 128 filters up a 3x3 layer is
 // >= 4x the work, one layer's weights (up to 1.2 MB) and two boards' activations no longer fit a CU the same way, and
 // the tiling is chosen per width and batch (run<T>() at the end of this file; DESIGN.md 5.3 has the anatomy, the
 // measurements and what was tried and dropped):
@@ -63,7 +63,7 @@ using f32x4s = __attribute__((ext_vector_type(4))) float;
 constexpr int PITCH = 12;
 constexpr int NPIX = 10 * PITCH;
 
-// same lane -> pixel map as tower_mfma.hip (conflict-free ds_read_b128 groups with PITCH 12)
+// same lane -> pixel map as the whole-network kernel (tower_common.h: PIXMAP; conflict-free ds_read_b128 groups with PITCH 12)
 __device__ __constant__ const unsigned char PIXMAP[32] = {
     0, 1, 2, 3, 8, 9, 10, 11, 12, 13, 14, 15, 4, 5, 6, 7,
     24, 25, 26, 27, 16, 17, 18, 19, 20, 21, 22, 23, 28, 29, 30, 31
@@ -127,8 +127,8 @@ struct ConvArgs {
 };
 
 // ---- weight stream of one (layer, 64-channel block): 8 KB chunks (4 k-steps x 2 row tiles) through a
-// 4-slot LDS ring by LDS-DMA, exactly the tower kernel's protocol (tower_mfma.hip: pipe_step) with
-// D = 4: the 4 waves of a workgroup would otherwise each pull the same fragments through the
+// 4-slot LDS ring by LDS-DMA (per chunk: a counted vmcnt wait, one s_barrier, then the refill of the slot
+// every wave has finished reading) with D = 4: the 4 waves of a workgroup would otherwise each pull the same fragments through the
 // vector L1 (128 B/clk wanted, 64 available).  The ring sits at LDS offset 0 (M0's 16-bit field).
 constexpr int RD = 4;
 constexpr int CHUNKB = 8192;
@@ -290,7 +290,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, RDN == 2
 #pragma unroll
             for (int k = 0; k < 4; ++k) Bq[0][k] = *reinterpret_cast<const V*>(smem + b_base + chunk_off(0) + k * 32);
         }
-        // one chunk step per iteration, fully unrolled: register set n & 1 holds chunk n (see tower_mfma.hip
+        // one chunk step per iteration, fully unrolled: register set n & 1 holds chunk n (see tower8_mfma.hip
         // for the ring protocol and the pinned read / MFMA interleave)
 #pragma unroll
         for (int n = 0; n < NCH; ++n) {

@@ -2,38 +2,21 @@
 // SPECIALISED waves: 512 threads per workgroup = 4 compute waves (one per SIMD: the MFMAs, the epilogues, the
 // softmax) + 4 helper waves (one per SIMD beside them: the weight stream's LDS-DMA, the plane ingest, the value FC).
 //
-// Why: tower_mfma.hip's four waves do everything themselves, and with ONE wave per SIMD every instruction that is
-// not an MFMA and does not fit a 24-cycle MFMA gap stops the matrix pipe.  Measured on that kernel (same-process A/B,
-// profiles/r03_tower_ablations_v1.txt; phase stamps, profiles/r03_tower_stamps_v1.txt): the two LDS-DMA pieces per
-// step cost 3.8 us of 36, the plane ingest keeps the matrix pipe idle for the first 9 500 cycles of 72 400, the heads'
-// VALU work and the value FC for most of the last 11 700.  A helper wave's VMEM / VALU / LDS instructions issue
-// beside the compute wave's MFMAs (different instruction types of different waves issue in the same cycle), so here
-// the compute waves' stream is: barrier, operand reads, MFMAs, epilogue.
+// Why: with four waves that do everything themselves (rounds 1-2's tower_kernel, retired: DESIGN §5.2b) and ONE wave
+// per SIMD, every instruction that is not an MFMA and does not fit a 24-cycle MFMA gap stops the matrix pipe.  Measured
+// on that kernel (same-process A/B, profiles/r03_tower_ablations_v1.txt; phase stamps, profiles/r03_tower_stamps_v1.txt):
+// the two LDS-DMA pieces per step cost 3.8 us of 36, the plane ingest keeps the matrix pipe idle for the first 9 500
+// cycles of 72 400, the heads' VALU work and the value FC for most of the last 11 700.  A helper wave's VMEM / VALU / LDS
+// instructions issue beside the compute wave's MFMAs (different instruction types of different waves issue in the same
+// cycle), so here the compute waves' stream is: barrier, operand reads, MFMAs, epilogue.
 //
-// Same data layout, same weight stream, same arithmetic in the same order as tower_mfma.hip (geometry and helpers:
-// tower_common.h): the convolutions' results are bit-identical to that kernel's (tools/tower_ablate.py).
+// Data layout, weight stream and LDS budget: tower_mfma.hip; geometry and helpers: tower_common.h.
 //
 // Barriers: s_barrier counts all 8 waves, so both roles execute exactly the same number of them per board group —
 // every barrier below is tagged [B..] in both paths.
 #include "tower_common.h"
 
 #include <atomic>
-#include <cstdlib>
-
-#ifndef KAMI_TOWER_STAMP
-#define KAMI_TOWER_STAMP 0
-#endif
-#if KAMI_TOWER_STAMP
-#define T8_STAMP(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0) stamps[wave * 32 + (k)] = t_; } while (0)
-#else
-#define T8_STAMP(k) do { } while (0)
-#endif
-
-// Timing-only ablations (diagnostic builds, -DKAMI_TOWER8_ABL=<bits>; results are NOT the network's): 1 no LDS-DMA in the
-// steps (the ring keeps its first chunks), 2 no activation reads in the regular steps, 4 no weight reads in them.
-#ifndef KAMI_TOWER8_ABL
-#define KAMI_TOWER8_ABL 0
-#endif
 
 namespace kh {
 
@@ -68,13 +51,17 @@ __device__ __forceinline__ unsigned cpipe_advance(CPipe& p)      // next chunk's
 __device__ __forceinline__ unsigned cpipe_step(CPipe& p)
 {
     asm volatile("s_barrier" ::: "memory");
-    // nothing moves across the step boundary (see tower_mfma.hip: the register double buffer would collapse)
+    // Nothing moves across the step boundary: hipcc otherwise hoists the next step's MFMAs up to their operand loads and
+    // the register double-buffering collapses into load -> wait -> MFMA.
     __builtin_amdgcn_sched_barrier(0);
     p.cslot = (p.cslot + 1 == RING_D) ? 0 : p.cslot + 1;
     return p.ring + p.cslot * CHUNK;
 }
 
-// A stream wave's half of a chunk: four 1 KB LDS-DMA pieces (tower_common.h's pipe_issue moves a quarter).
+// A stream wave's half of a chunk: four 1 KB LDS-DMA pieces (64 lanes x 16 B each -> LDS[M0 + inst offset + lane*16]).
+// Scalar base + one constant per-lane offset: no address VALU work per step; the instruction offset moves the global AND
+// the LDS address (verified on gfx950, tools/glds_test.hip).  M0 is written in the same statement that reads it and
+// restored (cdna_hip_programming.md §5.7).
 __device__ __forceinline__ void pipe_issue4(Pipe& p, int hw, int lane)
 {
     const char* sbase = p.stream + (size_t)p.next * CHUNK + hw * 4096;      // wave-uniform -> SGPR pair
@@ -94,17 +81,16 @@ __device__ __forceinline__ void pipe_issue4(Pipe& p, int hw, int lane)
 template <int VMX>
 __device__ __forceinline__ void hpipe_step(Pipe& p, int hw, int lane)
 {
-#if KAMI_TOWER8_ABL & 1
-    asm volatile("s_barrier" ::: "memory");
-#else
     asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * (RING_D - 3 - T8_LAG) + VMX) : "memory");
     asm volatile("s_barrier" ::: "memory");
     pipe_issue4(p, hw, lane);
-#endif
 }
 
 // ---------------------------------------------------------------- implicit-GEMM layer, compute-wave side
-// tower_mfma.hip's gemm_layer without the stream's issue side (template parameters as there).
+// A whole layer (tower_common.h: LayerShape), chunk by chunk.  PAR: register set of the layer's first chunk.  NREG: the
+// first NREG k-steps take their activation fragments from `breg` (the wave's own packed output of the previous layer,
+// see Packed) instead of the LDS image; CF as in b_offset.  TAILV > 0: the last chunk runs tile-major and the caller's
+// epilogue of tile 0 (TAILV vector ops per MFMA gap) is interleaved with tile 1's MFMAs.
 template <typename T, int TAPS, int KS, int MS, int PAR, int NREG = 0, bool CF = false, int TAILV = 0>
 __device__ __forceinline__ void gemm8_layer(CPipe& p, const char* smem, int lane, unsigned b_base, int stride,
                                             f32x16 (&acc)[MS], typename Elem<T>::vec8 (&A)[2][8],
@@ -154,7 +140,9 @@ __device__ __forceinline__ void gemm8_layer(CPipe& p, const char* smem, int lane
         for (int k = 0; k < KPC; ++k)
 #pragma unroll
             for (int ms = 0; ms < MS; ++ms) acc[ms] = Elem<T>::mfma(A[cur][k * MS + ms], B[cur][k], acc[ms]);
-        // the next chunk's operand reads go out two per MFMA from the top of the step
+        // Pin the interleave: the next chunk's operand reads go out two per MFMA from the top of the step.  Left alone hipcc
+        // sinks them to the end of the step and their latency lands on the next barrier; issued as one burst they measured
+        // 8 % slower than paced.
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // DS read
@@ -180,17 +168,12 @@ __device__ __forceinline__ void gemm8_dummy(CPipe& p, const char* smem, int lane
 // BARMID: step N0's barrier sits in the MIDDLE of the step (after four MFMAs) instead of at its top — used for the step
 // that follows a boundary(), whose own barrier comes late in the layer's first chunk.
 // k-step -> byte offset of its activation fragment from b_base.  BM_RASTER / BM_CENTRE: tower_common.h's b_offset without /
-// with the centre tap first; BM_HALVES / BM_QUARTERS: the 33..128-plane stem walked as two passes of 64 channels
-// (tower_mfma.hip's order) / four passes of 32 (this kernel's: the planes arrive and are converted quarter by quarter),
-// the order the packer lays the stream's weights out in.
-enum { BM_RASTER = 0, BM_CENTRE = 1, BM_HALVES = 2, BM_QUARTERS = 3 };
+// with the centre tap first; BM_QUARTERS: the 33..128-plane stem walked as four passes of 32 channels (the planes arrive
+// and are converted quarter by quarter), the order the packer lays the stream's weights out in.
+enum { BM_RASTER = 0, BM_CENTRE = 1, BM_QUARTERS = 2 };
 template <int TAPS, int KS, int BM>
 __device__ __forceinline__ constexpr unsigned b_off8(int kk, int stride)
 {
-    if constexpr (BM == BM_HALVES) {
-        const int pass = kk / (TAPS * KS / 2), k = kk % (TAPS * KS / 2);
-        return b_offset<TAPS, KS / 2, false>(k, stride) + pass * (KS / 2) * 32;
-    }
     if constexpr (BM == BM_QUARTERS) {
         const int pass = kk / (TAPS * KS / 4), k = kk % (TAPS * KS / 4);
         return b_offset<TAPS, KS / 4, false>(k, stride) + pass * (KS / 4) * 32;
@@ -247,15 +230,11 @@ __device__ __forceinline__ void gemm8_steps(CPipe& p, const char* smem, int lane
         }
         const unsigned a_off = cpipe_step(p) + lane * 16;
 #pragma unroll
-        for (int f = 0; f < 8; ++f) {
-            if ((KAMI_TOWER8_ABL & 4) && f > 0) A[nxt][f] = A[nxt][0];
-            else A[nxt][f] = *reinterpret_cast<const V*>(smem + a_off + f * 1024);
-        }
+        for (int f = 0; f < 8; ++f) A[nxt][f] = *reinterpret_cast<const V*>(smem + a_off + f * 1024);
         if (n + 1 < S::NCH) {
 #pragma unroll
             for (int k = 0; k < KPC; ++k) {
                 if ((n + 1) * KPC + k < NREG) B[nxt][k] = breg[(n + 1) * KPC + k];
-                else if ((KAMI_TOWER8_ABL & 2) && k > 0) B[nxt][k] = B[nxt][0];
                 else B[nxt][k] = *reinterpret_cast<const V*>(smem + b_base + b_off8<TAPS, KS, BM>((n + 1) * KPC + k, stride));
             }
         }
@@ -282,7 +261,7 @@ __device__ __forceinline__ void gemm8_steps(CPipe& p, const char* smem, int lane
 // Every micro-block below is fenced (sched_barrier): source order IS issue order.
 //   EPI_PACK   t = relu(acc), rounded to T first   (nn.cpp:30)
 //   EPI_RESID  x = x + relu(acc)                   (nn.cpp:31; with x = 0 also the stem's relu, nn.cpp:65)
-// Same operations on the same values as epilogue_pack / epilogue_residual: the same bits.
+// EPI_PACK is epilogue_pack's arithmetic (tower_common.h), one group at a time: the same bits.
 enum { EPI_STEM = 0, EPI_PACK = 1, EPI_RESID = 2 };
 
 template <typename T, int EPI, int G>
@@ -419,15 +398,8 @@ __device__ __forceinline__ void zero_halo(char* base, int board_bytes, int t)
 // The value head's second half on the four helper waves: valuefc + tanh -> [B][256] (nn.cpp:86-88), thread j = output j.
 // The row is requested behind [BL], waits in registers while the compute waves reduce their logits ([BS1], [BS2]) and
 // is used while they scale and store the policy rows: off the workgroup's tail.  v64: the value conv's [TW_NB][64] in LDS.
-#if KAMI_TOWER_STAMP
-#define FC_STAMP(k) do { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0) fc_stamps[k] = t_; } while (0)
-#define FC_STAMP_ARG , stamps + wave * 32
-#else
-#define FC_STAMP(k) do { } while (0)
-#define FC_STAMP_ARG
-#endif
 template <bool LEGAL>
-__device__ __forceinline__ void helper_value_fc(const TowerArgs& a, const float* v64, int b0, int j, int lane, unsigned long long* fc_stamps = nullptr)
+__device__ __forceinline__ void helper_value_fc(const TowerArgs& a, const float* v64, int b0, int j, int lane)
 {
     asm volatile("s_barrier" ::: "memory");                                                 // [BL]
     unsigned voff = (unsigned)j * 16u;        // (opaque: the optimiser would hoist 16 address pairs out of the group loop and spill them)
@@ -438,11 +410,8 @@ __device__ __forceinline__ void helper_value_fc(const TowerArgs& a, const float*
         fcw[k] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(a.fcw4) + (size_t)k * KH_VALUE_WIDTH * 16 + voff);
     const float fcbias = a.fcb[j];
     __builtin_amdgcn_sched_barrier(0);
-    FC_STAMP(10);
     asm volatile("s_barrier" ::: "memory");                                                 // [BS1]
-    FC_STAMP(11);
     asm volatile("s_barrier" ::: "memory");                                                 // [BS2]
-    FC_STAMP(12);
     // (the sums between [BS1] and [BS2] instead of behind [BS2]: no difference, 30.58 / 30.62 us on one device)
     float s[TW_NB];
 #pragma unroll
@@ -462,7 +431,6 @@ __device__ __forceinline__ void helper_value_fc(const TowerArgs& a, const float*
             s[bb] = fmaf(x.z, w.z, s[bb]); s[bb] = fmaf(x.w, w.w, s[bb]);
         }
     }
-    FC_STAMP(13);
     bool nan = false;
 #pragma unroll
     for (int bb = 0; bb < TW_NB; ++bb) {
@@ -470,11 +438,7 @@ __device__ __forceinline__ void helper_value_fc(const TowerArgs& a, const float*
             const float r = tanhf(s[bb] + fcbias);        // (1 - 2 / (1 + e^2x) on v_exp / v_rcp instead: no change, 32.05 vs 32.10 us — the
                                                           //  2 000 clocks between the sums and the end are the stores queueing behind the policy rows')
             nan |= (r != r);
-#if defined(T8_VFULL_PLAIN)
-            a.vfull[(size_t)(b0 + bb) * KH_VALUE_WIDTH + j] = r;
-#else
             store_wt(a.vfull + (size_t)(b0 + bb) * KH_VALUE_WIDTH + j, r);
-#endif
             if (LEGAL && j == 0) a.lg_values[b0 + bb] = r;               // column 0: the position's value
         }
     }
@@ -495,7 +459,7 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
     constexpr int LDS_L = LDS_X;
     using V = typename Elem<T>::vec8;
     // steps (= chunks = barriers) per board group, phase by phase: both roles walk exactly these
-    constexpr int NSTEM = LayerShape<9, KS_STEM, 2>::NCH;     // (33..128 planes: 2 x 9 chunks, the two 64-channel passes)
+    constexpr int NSTEM = LayerShape<9, KS_STEM, 2>::NCH;     // (33..128 planes: 18 chunks, four 32-channel passes)
     constexpr int P1 = NSTEM & 1;                            // register-set parity after the stem
     constexpr int NLAYER = LayerShape<9, TW_CP / 16, 2>::NCH;                                   // 9 per 3x3 layer
     constexpr int NPOL = LayerShape<1, TW_CP / 16, 4>::NCH + LayerShape<1, KH_POLICY_MID / 16, 4>::NCH + (P1 ? 1 : 0);
@@ -515,11 +479,6 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
     const float* vsh = vw + TW_CP;                          // [4]  folded valueconv/bn shift
     float* v64 = const_cast<float*>(vsh) + 4;               // [TW_NB][64] scratch
     float* red = v64 + TW_NB * 64;                          // [16] reduction scratch
-#if KAMI_TOWER_STAMP
-    unsigned long long* stamps = reinterpret_cast<unsigned long long*>(smem + ((LDS_PAR + tower_par_floats(6) * 4 + 15) & ~15));
-    if (lane == 0) stamps[wave * 32 + 30] = __builtin_amdgcn_s_memrealtime();
-    T8_STAMP(0);
-#endif
     const int ngroups = (a.B + TW_NB - 1) / TW_NB;
 
     if (wave >= 6) {
@@ -584,12 +543,9 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
                 // quarters have landed ~900 cycles after the last request and the pipeline is then free for the stem's
                 // weights (two quarters in flight and the others requested between the steps: 0.4 % slower, same device)
                 request(0); request(1); request(2); request(3);
-                T8_STAMP(6);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) convert(0, j);
-                T8_STAMP(8);
                 lds_barrier();                                                              // [B0]
-                T8_STAMP(2);
                 // quarter q's first chunk is chunk (18 q + 3) / 4 = 0, 4, 9, 13: read behind that step's barrier
                 //   slot (between barriers)   s0 s1 s2 s3 | s4 s5 s6 s7 s8 | s9 s10 s11 s12 | ...
                 //   items converted           q1: 2 2 2 2 | q2: 2 2 2 1 1  | q3: 2  2   2   2
@@ -667,10 +623,8 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
                     if (__any(bad) && lane == 0) raise_flag<LEGAL>(a, 0);
                 }
                 lds_barrier();                                                              // [B0]
-                T8_STAMP(2);
                 for (int i = 0; i < NSTEM; ++i) asm volatile("s_barrier" ::: "memory");     // [stem steps]
             }
-            T8_STAMP(5);
             const int nsteps = 2 * R * NLAYER + NPOL;
             for (int i = 0; i < nsteps; ++i) {
                 asm volatile("s_barrier" ::: "memory");                                     // [tower + policy steps]
@@ -681,11 +635,8 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 }
             }
-            T8_STAMP(19);
-            helper_value_fc<LEGAL>(a, v64, b0, tid & 255, lane FC_STAMP_ARG);                            // [BL] [BS1] [BS2] inside
-            T8_STAMP(21);
+            helper_value_fc<LEGAL>(a, v64, b0, tid & 255, lane);                            // [BL] [BS1] [BS2] inside
             asm volatile("s_barrier" ::: "memory");                                         // [BE]
-            T8_STAMP(22);
         }
     } else if (wave >= 4) {
         // =====================================================================================  stream waves (2)
@@ -693,22 +644,18 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
         const int hw = wave - 4;
         const int nsteps = NSTEM + 2 * R * NLAYER + NPOL;
         Pipe pipe;
-        pipe.stream = a.wstream; pipe.nch = a.nchunks; pipe.next = 0; pipe.islot = 0; pipe.cslot = 0; pipe.ring = LDS_RING;
+        pipe.stream = a.wstream; pipe.nch = a.nchunks; pipe.next = 0; pipe.islot = 0; pipe.ring = LDS_RING;
 #pragma unroll
         for (int i = 0; i < RING_D - 1; ++i) pipe_issue4(pipe, hw, lane);
 
         for (int grp = blockIdx.x; grp < ngroups; grp += gridDim.x) {
             // chunks 0 and 1 of this group have landed (chunks 2, 3, 4 may still be in flight)
             asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(4 * (RING_D - 3)) : "memory");                 // [B0]
-            T8_STAMP(2);
             for (int i = 0; i < nsteps; ++i) hpipe_step<0>(pipe, hw, lane);
-            T8_STAMP(19);
             // (the stream is at rest until the next group's first step: these loads and stores are the youngest
             //  operations, every ring piece older than them has long landed)
-            helper_value_fc<LEGAL>(a, v64, grp * TW_NB, tid & 255, lane FC_STAMP_ARG);                   // [BL] [BS1] [BS2] inside
-            T8_STAMP(21);
+            helper_value_fc<LEGAL>(a, v64, grp * TW_NB, tid & 255, lane);                   // [BL] [BS1] [BS2] inside
             asm volatile("s_barrier" ::: "memory");                                         // [BE]
-            T8_STAMP(22);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // drain the prefetch ring before exit
     } else {
@@ -745,7 +692,6 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
                 if (i0 + 768 + ct < n4) dst[i0 + 768 + ct] = v3;
             }
         }
-        T8_STAMP(1);
 
         V A[2][8];                             // two register sets of weight fragments (current / next chunk)
         bool first = true;
@@ -755,7 +701,6 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
             // zero the halo pixels of X and S (the previous group's logits lived there); the helpers fill S's interior
             zero_halo<XSTR>(smem + LDS_X, XBOARD, ct);
             zero_halo<SSTR>(smem + LDS_ST, SBOARD, ct);
-            T8_STAMP(2);
             lds_barrier();                                                                  // [B0]
             if (first) {
                 first = false;
@@ -769,7 +714,6 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
             f32x16 xf[2];          // the same tile in fp32: the skip operand and the value head's input
 #pragma unroll
             for (int i = 0; i < 16; ++i) { xf[0][i] = 0.0f; xf[1][i] = 0.0f; }
-            T8_STAMP(3);
             // ---- stem: conv1 + batchnorm1 + relu, S -> X (nn.cpp:62-65): all but its last chunk
             f32x16 accA[2], accB[2];       // the running layer's sums / the next layer's (alternating roles)
             V B[2][4];
@@ -781,27 +725,25 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
                 for (int k = 0; k < 4; ++k) B[0][k] = *reinterpret_cast<const V*>(smem + sin + b_off8<9, KS_STEM, BMS>(k, SSTR));
                 gemm8_steps<T, 9, KS_STEM, 2, 0, 0, BMS, 0, NSTEM - 1>(pipe, smem, lane, sin, SSTR, accA, A, B);
             }
-            T8_STAMP(4);
             // (T shares LDS with S and the tower's image reads go through T's halo: the helper waves clear it behind the
             //  first tower step's barrier, after every wave's last read of S and long before conv2 of the first block.)
             constexpr int CP1 = P1 ^ 1;      // register set of the last chunk of the stem and of every conv2
             // ---- residual tower: x = x + relu(bn2(conv2(relu(bn1(conv1 x)))))   nn.cpp:26-34
             // The stem's end is a residual end with x = 0 (0 + relu(acc) = relu(acc) exactly): ONE boundary form at the
             // loop's top, one tail behind it, no branch inside.
-            T8_STAMP(5);
             for (int r = 0; r < R; ++r) {
                 boundary<T, EPI_RESID, CP1>(pipe, smem, lane, accA, accB, sh0 + (1 + 2 * r) * TW_CP * 4, A, B, xf, xout_h, xin);
                 gemm8_steps<T, 9, TW_CP / 16, 2, P1, 4, BM_CENTRE, 1, 8, true>(pipe, smem, lane, xin, XSTR, accB, A, B);        // conv1
-                T8_STAMP(6 + 2 * r);
                 boundary<T, EPI_PACK, P1>(pipe, smem, lane, accB, accA, sh0 + (2 + 2 * r) * TW_CP * 4, A, B, xf, tout_h, tin);
                 gemm8_steps<T, 9, TW_CP / 16, 2, P1 ^ 1, 4, BM_CENTRE, 1, 8, true>(pipe, smem, lane, tin, XSTR, accA, A, B);    // conv2
-                T8_STAMP(7 + 2 * r);
             }
             tower_tail<T, EPI_RESID, CP1>(pipe, smem, lane, accA, A, B, xf, xk);
 
-            // ---- value head, first half: valueconv + vbatchnorm + relu (nn.cpp:83-85) on the fp32 tile (see
-            //      tower_mfma.hip 4a: four partial sums, halves joined by one v_permlane32_swap; a NaN or Inf anywhere
-            //      in the residual stream makes the partial sum non-finite: the poisoned-stream detector)
+            // ---- value head, first half: valueconv + vbatchnorm + relu (nn.cpp:83-85) on the fp32 tile: each lane holds
+            //      32 of its pixel's 64 channels, its partner lane (+-32) the rest.  Four independent partial sums (a single
+            //      fma chain is latency-bound with one wave per SIMD), halves joined by one v_permlane32_swap.  A NaN or Inf
+            //      anywhere in the residual stream makes the partial sum non-finite (x*w, w finite): that is the poisoned-
+            //      stream detector for the ReLUs' NaN squashing (see relu_nan)
             {
                 f32x2 s01 = { 0.0f, 0.0f }, s23 = { 0.0f, 0.0f };
 #pragma unroll
@@ -821,7 +763,6 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
                 const float sv = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
                 if (h == 0) v64[wb * 64 + py * 8 + px] = relu_nan(sv + vsh[0]);
             }
-            T8_STAMP(18);
 
             // ---- policy head: policyconv + pbatchnorm + relu (nn.cpp:72-74), 1x1: the operand is the wave's own tile
             Packed<4> pk;
@@ -832,7 +773,6 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
                 acc_init<4>(acc, pshift1, h);
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // v64 written before the next barrier
                 gemm8_layer<T, 1, TW_CP / 16, 4, P1, 4>(pipe, smem, lane, 0, 0, acc, A, bf);
-                T8_STAMP(19);
                 epilogue_pack<T, 4>(acc, pk);
             }
             // ---- policyconv2 (+bias): -> logits L[board][pixel*73 + plane]      nn.cpp:75-79
@@ -855,7 +795,6 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
                         }
                 lds_barrier();                                                              // [BL]
             }
-            T8_STAMP(20);
 
             // ---- softmax over all 4672 logits of a board (nn.cpp:80): 128 threads per board, one LDS pass, each
             //      thread keeps its <= 10 float4 in registers
@@ -896,8 +835,10 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
                 const float inv = 1.0f / (red[4 + bb * 2] + red[4 + bb * 2 + 1]);
                 bool nan = false;
                 if (LEGAL) {
-                    // legal-move mode: the board's first wave does what gather_legal_kernel does with the stored row
-                    // (tower_mfma.hip 4d: the same operations on the same values in the same order: the same bits)
+                    // legal-move mode: the board's first wave does what gather_legal_kernel does with the stored row — p[a] =
+                    // exp(l[a] - m) * inv recomputed from the logits in LDS (the same operations on the same values: the
+                    // same bits), summed and renormalised in that kernel's order (__fmul_rn: the row's entries are rounded
+                    // products; no contraction into the sum)
                     nan = inv != inv;                           // a NaN logit makes the sum, hence every entry, NaN
                     if (live && (cw & 1) == 0) {
                         const float* Lb = reinterpret_cast<const float*>(smem + LDS_L + bb * LBOARD);
@@ -930,26 +871,14 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
                 }
                 if (__any(nan) && lane == 0) raise_flag<LEGAL>(a, 0);
             }
-            T8_STAMP(21);
             lds_barrier();      // [BE] L / v64 are dead; the next group may overwrite them
-            T8_STAMP(22);
         }
     }
-#if KAMI_TOWER_STAMP
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    T8_STAMP(23);
-    if (lane == 0) stamps[wave * 32 + 31] = __builtin_amdgcn_s_memrealtime();
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    // compute waves over the workgroup's first value row, helper waves over its second (256 floats = 4 waves x 32 stamps)
-    if (lane < 32 && (int)blockIdx.x * TW_NB + 1 < a.B)
-        reinterpret_cast<unsigned long long*>(a.vfull + ((size_t)blockIdx.x * TW_NB + (wave >> 2)) * KH_VALUE_WIDTH)[cw * 32 + lane] = stamps[wave * 32 + lane];
-#endif
 }
 
-template <typename T, int KS_STEM, bool LEGAL = false> static hipError_t launch8(const TowerArgs& a, int grid, hipStream_t s)
+template <typename T, int KS_STEM, bool LEGAL = false> static hipError_t launch(const TowerArgs& a, int grid, hipStream_t s)
 {
-    constexpr int FP = KS_STEM * 16;
-    const int lds = LDS_ST + st_size(FP) + tower_par_floats(a.R) * 4 + (KAMI_TOWER_STAMP ? 16 + 8 * 32 * 8 : 0);
+    const int lds = tower_lds_bytes(KS_STEM * 16, a.R);
     static std::atomic<bool> attr_done{ false };      // engines are called from many host threads; setting it twice is harmless
     if (!attr_done.load(std::memory_order_acquire)) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tower8_kernel<T, KS_STEM, LEGAL>),
@@ -961,16 +890,16 @@ template <typename T, int KS_STEM, bool LEGAL = false> static hipError_t launch8
     return hipGetLastError();
 }
 
-hipError_t launch_tower8(int dtype, int FP, const TowerArgs& a, int num_cus, hipStream_t s)
+hipError_t launch_tower(int dtype, int FP, const TowerArgs& a, int num_cus, hipStream_t s)
 {
     const int ngroups = (a.B + TW_NB - 1) / TW_NB;
     const int grid = ngroups < num_cus ? ngroups : num_cus;      // one workgroup per CU (LDS-bound residency)
     if (a.lg_offsets) {                      // legal-move mode: compact records (F <= 32) only
         if (FP != 32 || !a.lg_actions || !a.lg_priors || !a.lg_values || !a.lg_flags) return hipErrorInvalidValue;
-        return dtype == KH_BF16 ? launch8<__bf16, 2, true>(a, grid, s) : launch8<_Float16, 2, true>(a, grid, s);
+        return dtype == KH_BF16 ? launch<__bf16, 2, true>(a, grid, s) : launch<_Float16, 2, true>(a, grid, s);
     }
-    if (dtype == KH_BF16) return FP == 32 ? launch8<__bf16, 2>(a, grid, s) : launch8<__bf16, 8>(a, grid, s);
-    return FP == 32 ? launch8<_Float16, 2>(a, grid, s) : launch8<_Float16, 8>(a, grid, s);
+    if (dtype == KH_BF16) return FP == 32 ? launch<__bf16, 2>(a, grid, s) : launch<__bf16, 8>(a, grid, s);
+    return FP == 32 ? launch<_Float16, 2>(a, grid, s) : launch<_Float16, 8>(a, grid, s);
 }
 
 }  // namespace kh

@@ -1,5 +1,5 @@
-// tower_common.h — geometry, MFMA fragment helpers, the LDS-DMA weight ring and the epilogues shared by the two
-// whole-network kernels (tower_mfma.hip: 4 waves per workgroup; tower8_mfma.hip: 4 compute + 4 helper waves).
+// tower_common.h — geometry, MFMA fragment helpers, the LDS-DMA weight ring's state and the epilogues of the
+// whole-network kernel (tower8_mfma.hip; overview and LDS layout: tower_mfma.hip).
 #pragma once
 #include "kh_internal.h"
 #include "encode_square.h"
@@ -21,10 +21,7 @@ constexpr int XBOARD = NPIX * XSTR;             // 17 280
 constexpr int PSTR = KH_POLICY_MID * 2 + 16;    // 272: pixel stride of the policy mid image
 constexpr int PBOARD = 64 * PSTR;               // dense 64 pixels (1x1 conv needs no halo)
 constexpr int LBOARD = KH_PSIZE * 4;            // logits fp32 per board
-#ifndef KAMI_RING_D
-#define KAMI_RING_D 6
-#endif
-constexpr int RING_D = KAMI_RING_D;      // (7 fits the LDS too: tried for one more step of prefetch lead, see DESIGN)
+constexpr int RING_D = 6;                       // (7 fits the LDS too: tried for one more step of prefetch lead, see DESIGN)
 constexpr int CHUNK = 8192;                     // 8 fragments of 1 KB
 // The DMA ring sits at LDS offset 0 so that its addresses fit M0's 16-bit LDS offset field.
 constexpr int LDS_RING = 0;
@@ -78,8 +75,6 @@ __device__ __forceinline__ unsigned relu_pk(unsigned w)
     const short2_t z = { 0, 0 };
     return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(short2_t, w), z));
 }
-template <typename T> __device__ __forceinline__ float unpack_lo(unsigned u) { return (float)__builtin_bit_cast(T, (unsigned short)(u & 0xffffu)); }
-template <typename T> __device__ __forceinline__ float unpack_hi(unsigned u) { return (float)__builtin_bit_cast(T, (unsigned short)(u >> 16)); }
 
 // ReLU as one integer max.  It squashes negative-signed NaNs (torch::relu keeps NaN), so the kernel guards
 // the reference's NaN contract (nn.cpp:176-180) elsewhere: non-finite input planes are flagged
@@ -92,28 +87,9 @@ struct Pipe {
     const char* stream;     // packed fragments, nch chunks of 8 KB, cyclic
     int nch;
     int next;               // chunk index to issue next
-    int islot, cslot;       // ring slots: next to fill / next to consume
+    int islot;              // ring slot to fill next
     unsigned ring;          // LDS byte offset of the ring
 };
-
-// One wave's quarter of a chunk: two 1 KB LDS-DMA pieces (64 lanes x 16 B each -> LDS[M0 + inst
-// offset + lane*16]).  Scalar base + one constant per-lane offset: no address VALU work per step;
-// the instruction offset moves the global AND the LDS address (verified on gfx950,
-// tools/glds_test.hip).  M0 is written in the same statement that reads it and restored
-// (cdna_hip_programming.md §5.7).
-__device__ __forceinline__ void pipe_issue(Pipe& p, int wave, int lane)
-{
-    const char* sbase = p.stream + (size_t)p.next * CHUNK + wave * 2048;      // wave-uniform -> SGPR pair
-    const unsigned dst = p.ring + p.islot * CHUNK + wave * 2048;
-    const unsigned voff = lane * 16;
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(voff), "s"(sbase), "s"(dst) : "memory");
-    p.next = (p.next + 1 == p.nch) ? 0 : p.next + 1;
-    p.islot = (p.islot + 1 == RING_D) ? 0 : p.islot + 1;
-}
 
 __device__ __forceinline__ void lds_barrier()
 {
@@ -162,8 +138,8 @@ __device__ __forceinline__ void acc_init(f32x16 (&acc)[MS], const float* shift, 
 // of this lane's pixel (the MFMA C/D layout: 4 consecutive channels per register group).
 template <int MS> struct Packed { u32x2 o[MS][4]; };
 
-// ReLU and convert (conv1 of a block, policyconv): convert first, then ReLU on the packed pairs —
-// half the VALU work of clamping the 32 fp32 values.
+// ReLU and convert (policyconv; boundary()'s EPI_PACK does the same per group for conv1 of a block):
+// convert first, then ReLU on the packed pairs — half the VALU work of clamping the 32 fp32 values.
 template <typename T, int MS>
 __device__ __forceinline__ void epilogue_pack(const f32x16 (&acc)[MS], Packed<MS>& pk)
 {
@@ -184,37 +160,6 @@ __device__ __forceinline__ void epilogue_pack(const f32x16 (&acc)[MS], Packed<MS
             pk.o[ms][g].y = relu_pk(c[2 * g + 1]);
         }
     }
-}
-
-// End of a residual block (and the stem): xf = (SKIP ? xf : 0) + relu(acc) in fp32 — the residual
-// stream of the wave's own pixels stays in fp32 registers (nn.cpp:31 adds in fp32 too), only the
-// copies that feed the MFMAs are rounded to T.
-template <typename T, bool SKIP>
-__device__ __forceinline__ void epilogue_residual(const f32x16 (&acc)[2], f32x16 (&xf)[2], Packed<2>& pk)
-{
-#pragma unroll
-    for (int ms = 0; ms < 2; ++ms) {
-        f32x16 t;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) t[i] = relu_nan(acc[ms][i]);
-        xf[ms] = SKIP ? xf[ms] + t : t;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            pk.o[ms][g].x = pack2<T>(xf[ms][4 * g + 0], xf[ms][4 * g + 1]);
-            pk.o[ms][g].y = pack2<T>(xf[ms][4 * g + 2], xf[ms][4 * g + 3]);
-        }
-    }
-}
-
-// 8-byte packed stores of the tile to an LDS image (for the neighbouring pixels' taps).
-template <int MS>
-__device__ __forceinline__ void store_packed(const Packed<MS>& pk, char* smem, unsigned out_pix, int h)
-{
-#pragma unroll
-    for (int ms = 0; ms < MS; ++ms)
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-            *reinterpret_cast<u32x2*>(smem + out_pix + (ms * 32 + 8 * g + 4 * h) * 2) = pk.o[ms][g];
 }
 
 // The packed tile as MFMA B fragments: k-step ks, slot j of lane (r, h) = channel
@@ -252,48 +197,6 @@ __device__ __forceinline__ void raise_flag(const TowerArgs& a, int which)
 {
     atomicOr(&a.flags[which], 1);
     if (LEGAL) __builtin_nontemporal_store(1, a.lg_flags + which);
-}
-
-// Second stage of the 128-plane ingest: one half (64 channels) of this thread's four (board, pixel)
-// items -> T in the S image; flags non-finite inputs like the reference's NaN check (nn.cpp:176).
-template <typename T>
-__device__ __forceinline__ void ingest_half(const float4_u (&v)[4][2], int hh, char* simg, int sstr, int sboard,
-                                            int b0, int tid, int lane, const TowerArgs& a)
-{
-    const int F = a.F;
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int bp = (tid >> 3) + 32 * j, bb = bp >> 6, p = bp & 63;
-        const bool live = (b0 + bb) < a.B;
-        char* dst = simg + bb * sboard + (((p >> 3) + 1) * PITCH + (p & 7) + 1) * sstr + hh * 128 + 8 * (tid & 7);
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int c = hh * 64 + 32 * q + 4 * (tid & 7);
-            const int sh = c - min(c, F - 4);         // the load was moved back by sh channels; channels >= F are zero
-            float x[4] = { v[j][q].x, v[j][q].y, v[j][q].z, v[j][q].w };
-            if (sh != 0) {
-                float y[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    y[k] = 0.0f;
-#pragma unroll
-                    for (int m = 1; m < 4; ++m)
-                        if (k + m < 4 && sh == m) y[k] = x[k + m];
-                }
-#pragma unroll
-                for (int k = 0; k < 4; ++k) x[k] = y[k];
-            }
-            u32x2 o = { 0u, 0u };
-            if (live) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) bad = bad || ((__float_as_uint(x[k]) & 0x7f800000u) == 0x7f800000u);
-                o.x = pack2<T>(x[0], x[1]); o.y = pack2<T>(x[2], x[3]);
-            }
-            *reinterpret_cast<u32x2*>(dst + 64 * q) = o;
-        }
-    }
-    if (__any(bad) && lane == 0) raise_flag<false>(a, 0);
 }
 
 }  // namespace kh

@@ -128,8 +128,10 @@ def test_forward_mfma_vs_reference_fixtures(net_fixture, dtype):
 
 @pytest.mark.parametrize("dtype", ["f16", "bf16"])
 @pytest.mark.parametrize("F,C,R,B", [(119, 64, 6, 64), (30, 64, 6, 33), (30, 24, 1, 7), (119, 64, 0, 3),
-                                     # 33..128 planes take the two-pass stem: ragged rows on both sides of the split
-                                     (33, 64, 1, 5), (61, 48, 1, 3), (64, 64, 1, 4), (67, 64, 1, 3), (100, 64, 2, 7), (128, 64, 1, 2)])
+                                     # 33..128 planes take the four-pass stem: ragged rows on both sides of the splits
+                                     (33, 64, 1, 5), (61, 48, 1, 3), (64, 64, 1, 4), (67, 64, 1, 3), (100, 64, 2, 7), (128, 64, 1, 2),
+                                     # the headline net at a batch with an odd last board group and at a small one
+                                     (119, 64, 6, 37), (119, 64, 6, 16)])
 def test_forward_mfma_vs_oracle(dtype, F, C, R, B):
     blob = W.random_weights(F, C, R, seed=F + C + R, peaky=20.0)
     x = np.random.default_rng(B).random((B, 8, 8, F), dtype=np.float32)
@@ -172,8 +174,8 @@ def test_mfma_nan_guard():
 
 @pytest.mark.parametrize("ch", [0, 63, 64, 118])
 def test_mfma_nan_guard_two_pass_stem(ch):
-    """F = 119 ingests the planes in two halves (channels < 64 before the stem, the rest under it):
-    a non-finite plane in either half, in the last board of an odd batch, is still flagged."""
+    """F = 119 ingests the planes in four quarters of 32 channels (the first before the stem, the rest under it):
+    a non-finite plane in any quarter, in the last board of an odd batch, is still flagged."""
     F, C, R = 119, 64, 1
     nn = NN(8, 8, F, 4672, filters=C, residuals=R, dtype="bf16")
     nn.load_weights(W.random_weights(F, C, R, seed=3), 1)
