@@ -403,7 +403,17 @@ int build_tower(Weights& W, const HostNet& n, int dtype, int F, int C, int R)
     pack_layer(stream, dtype, n.pconv.w, sc.data(), KH_POLICY_MID, C, 1, TW_CP / 16, 4, 0, false, TW_CP / 16);
     float* pbias2 = pshift1 + KH_POLICY_MID;
     memcpy(pbias2, n.p2b, sizeof(float) * KH_POLICY_PLANES);
-    pack_layer(stream, dtype, n.p2w, nullptr, KH_POLICY_PLANES, KH_POLICY_MID, 1, KH_POLICY_MID / 16, 4, 0, false, KH_POLICY_MID / 16);
+    {
+        // 73 planes on three 32-row tiles: a chunk holds 2 k-steps x 3 tiles = 6 fragments, padded to the ring's 8 KB
+        std::vector<uint16_t> p2;
+        pack_layer(p2, dtype, n.p2w, nullptr, KH_POLICY_PLANES, KH_POLICY_MID, 1, KH_POLICY_MID / 16, 3, 0, false, KH_POLICY_MID / 16, false);
+        constexpr size_t FRAG = 512, CHUNK_FRAGS = 6;
+        if (p2.size() != (size_t)(KH_POLICY_MID / 16) * 3 * FRAG) return fail(KH_ERR_INVALID, "internal: policyconv2 stream size");
+        for (size_t c = 0; c < p2.size(); c += CHUNK_FRAGS * FRAG) {
+            stream.insert(stream.end(), p2.begin() + c, p2.begin() + c + CHUNK_FRAGS * FRAG);
+            stream.resize(stream.size() + (8 - CHUNK_FRAGS) * FRAG, 0);
+        }
+    }
     if (((stream.size() / 4096) & 1) != 0) stream.resize(stream.size() + 4096, 0);   // parity chunk (see gemm8_dummy)
     float* vw = pbias2 + 128;
     float vs, vsh;

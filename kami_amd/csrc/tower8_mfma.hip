@@ -99,6 +99,7 @@ __device__ __forceinline__ void gemm8_layer(CPipe& p, const char* smem, int lane
     using V = typename Elem<T>::vec8;
     using S = LayerShape<TAPS, KS, MS>;
     constexpr int KPC = S::KPC;
+    constexpr int NF = KPC * MS;       // fragments a chunk of this layer uses (MS = 3: 6 of the 8 KB chunk's 8)
     V B[2][KPC];
 #pragma unroll
     for (int k = 0; k < KPC; ++k) {
@@ -110,7 +111,8 @@ __device__ __forceinline__ void gemm8_layer(CPipe& p, const char* smem, int lane
         const int cur = (PAR + n) & 1, nxt = cur ^ 1;
         const unsigned a_off = cpipe_step(p) + lane * 16;
 #pragma unroll
-        for (int f = 0; f < 8; ++f) A[nxt][f] = *reinterpret_cast<const V*>(smem + a_off + f * 1024);
+        for (int f = 0; f < 8; ++f)      // (the last step reads the next layer's first chunk: all 8)
+            if (n + 1 == S::NCH || f < NF) A[nxt][f] = *reinterpret_cast<const V*>(smem + a_off + f * 1024);
         if (n + 1 < S::NCH) {
 #pragma unroll
             for (int k = 0; k < KPC; ++k) {
@@ -144,7 +146,7 @@ __device__ __forceinline__ void gemm8_layer(CPipe& p, const char* smem, int lane
         // sinks them to the end of the step and their latency lands on the next barrier; issued as one burst they measured
         // 8 % slower than paced.
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
+        for (int i = 0; i < NF; ++i) {
             __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   // DS read
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
         }
@@ -396,7 +398,7 @@ __device__ __forceinline__ void zero_halo(char* base, int board_bytes, int t)
 }
 
 // The value head's second half on the four helper waves: valuefc + tanh -> [B][256] (nn.cpp:86-88), thread j = output j.
-// The row is requested behind [BL], waits in registers while the compute waves reduce their logits ([BS1], [BS2]) and
+// The row is requested behind [BL], waits in registers while the compute waves sum their exponentials ([BS2]) and
 // is used while they scale and store the policy rows: off the workgroup's tail.  v64: the value conv's [TW_NB][64] in LDS.
 template <bool LEGAL>
 __device__ __forceinline__ void helper_value_fc(const TowerArgs& a, const float* v64, int b0, int j, int lane)
@@ -410,9 +412,7 @@ __device__ __forceinline__ void helper_value_fc(const TowerArgs& a, const float*
         fcw[k] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(a.fcw4) + (size_t)k * KH_VALUE_WIDTH * 16 + voff);
     const float fcbias = a.fcb[j];
     __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_barrier" ::: "memory");                                                 // [BS1]
     asm volatile("s_barrier" ::: "memory");                                                 // [BS2]
-    // (the sums between [BS1] and [BS2] instead of behind [BS2]: no difference, 30.58 / 30.62 us on one device)
     float s[TW_NB];
 #pragma unroll
     for (int bb = 0; bb < TW_NB; ++bb) s[bb] = 0.0f;
@@ -462,7 +462,7 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
     constexpr int NSTEM = LayerShape<9, KS_STEM, 2>::NCH;     // (33..128 planes: 18 chunks, four 32-channel passes)
     constexpr int P1 = NSTEM & 1;                            // register-set parity after the stem
     constexpr int NLAYER = LayerShape<9, TW_CP / 16, 2>::NCH;                                   // 9 per 3x3 layer
-    constexpr int NPOL = LayerShape<1, TW_CP / 16, 4>::NCH + LayerShape<1, KH_POLICY_MID / 16, 4>::NCH + (P1 ? 1 : 0);
+    constexpr int NPOL = LayerShape<1, TW_CP / 16, 4>::NCH + LayerShape<1, KH_POLICY_MID / 16, 3>::NCH + (P1 ? 1 : 0);
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -635,7 +635,7 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
                     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
                 }
             }
-            helper_value_fc<LEGAL>(a, v64, b0, tid & 255, lane);                            // [BL] [BS1] [BS2] inside
+            helper_value_fc<LEGAL>(a, v64, b0, tid & 255, lane);                            // [BL] [BS2] inside
             asm volatile("s_barrier" ::: "memory");                                         // [BE]
         }
     } else if (wave >= 4) {
@@ -654,7 +654,7 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
             for (int i = 0; i < nsteps; ++i) hpipe_step<0>(pipe, hw, lane);
             // (the stream is at rest until the next group's first step: these loads and stores are the youngest
             //  operations, every ring piece older than them has long landed)
-            helper_value_fc<LEGAL>(a, v64, grp * TW_NB, tid & 255, lane);                   // [BL] [BS1] [BS2] inside
+            helper_value_fc<LEGAL>(a, v64, grp * TW_NB, tid & 255, lane);                   // [BL] [BS2] inside
             asm volatile("s_barrier" ::: "memory");                                         // [BE]
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // drain the prefetch ring before exit
@@ -776,28 +776,36 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
                 epilogue_pack<T, 4>(acc, pk);
             }
             // ---- policyconv2 (+bias): -> logits L[board][pixel*73 + plane]      nn.cpp:75-79
+            //      and the softmax's row max, reduced from the same registers and published with L
             {
-                f32x16 acc[4];                  // 73 planes padded to 128 rows: whole 2-k-step chunks
+                f32x16 acc[3];                  // 73 planes on three 32-row tiles (rows 73..95 are padding)
                 V bf[8];
                 packed_fragments<T, 4>(pk, bf);
-                acc_init<4>(acc, pbias2, h);
-                gemm8_layer<T, 1, KH_POLICY_MID / 16, 4, P1, 8>(pipe, smem, lane, 0, 0, acc, A, bf);
+                acc_init<3>(acc, pbias2, h);
+                gemm8_layer<T, 1, KH_POLICY_MID / 16, 3, P1, 8>(pipe, smem, lane, 0, 0, acc, A, bf);
                 if (P1) gemm8_dummy<T, 1>(pipe, smem, lane, A);      // stream parity back to 0 for the next group
                 float* lrow = reinterpret_cast<float*>(smem + LDS_L + wb * LBOARD) + (py * 8 + px) * KH_POLICY_PLANES;
+                float m = -INFINITY;
 #pragma unroll
-                for (int ms = 0; ms < 3; ++ms)      // planes >= 96 are padding
+                for (int ms = 0; ms < 3; ++ms)
 #pragma unroll
                     for (int g = 0; g < 4; ++g)
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
                             const int plane = ms * 32 + 8 * g + 4 * h + i;
-                            if (plane < KH_POLICY_PLANES) lrow[plane] = acc[ms][4 * g + i];
+                            if (plane < KH_POLICY_PLANES) {
+                                lrow[plane] = acc[ms][4 * g + i];
+                                m = fmaxf(m, acc[ms][4 * g + i]);
+                            }
                         }
+                // the max of a set: the same m (fmaxf, NaNs skipped) as a pass over the row in any order
+                m = wave_max_f(m);
+                if (lane == 0) red[cw] = m;
                 lds_barrier();                                                              // [BL]
             }
 
             // ---- softmax over all 4672 logits of a board (nn.cpp:80): 128 threads per board, one LDS pass, each
-            //      thread keeps its <= 10 float4 in registers
+            //      thread keeps its <= 10 float4 in registers; the row max came with L
             {
                 const int bb = ct >> 7, tt = ct & 127;
                 const bool live = (b0 + bb) < a.B;
@@ -809,19 +817,13 @@ __global__ __launch_bounds__(512) void tower8_kernel(TowerArgs a)
                     const int q = tt + 128 * k;
                     v[k] = (q < NQ) ? L4[q] : make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
                 }
+                const float m = fmaxf(red[bb * 2], red[bb * 2 + 1]);
                 if (a.logits && live) {
                     float4* lo = reinterpret_cast<float4*>(a.logits + (size_t)(b0 + bb) * KH_PSIZE);
 #pragma unroll
                     for (int k = 0; k < 10; ++k)
                         if (tt + 128 * k < NQ) lo[tt + 128 * k] = v[k];
                 }
-                float m = -INFINITY;
-#pragma unroll
-                for (int k = 0; k < 10; ++k) m = fmaxf(fmaxf(m, fmaxf(v[k].x, v[k].y)), fmaxf(v[k].z, v[k].w));
-                m = wave_max_f(m);
-                if (lane == 0) red[cw] = m;
-                lds_barrier();                                                              // [BS1]
-                m = fmaxf(red[bb * 2], red[bb * 2 + 1]);
                 float s = 0.0f;
 #pragma unroll
                 for (int k = 0; k < 10; ++k) {
