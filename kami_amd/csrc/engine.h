@@ -1,0 +1,188 @@
+// engine.h — the engine's host-side state and the declarations its translation units share: kh_api.hip (C ABI, slots,
+// forward wrappers, host and device I/O, kh_train, checkpoints), weights.hip (parameter sets) and queue.hip (the
+// coalescing queue).  Not part of the public boundary (that is include/kami_hip.h).
+#pragma once
+#include "kh_internal.h"
+
+#include <atomic>
+#include <condition_variable>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <vector>
+
+namespace kh {
+
+extern thread_local std::string g_err;   // what kh_last_error() returns: the calling thread's last failure
+
+int fail(int code, const char* fmt, ...);
+
+#define HIPCHK(expr)                                                                         \
+    do {                                                                                     \
+        hipError_t _e = (expr);                                                              \
+        if (_e != hipSuccess)                                                                \
+            return fail(KH_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e),   \
+                        __FILE__, __LINE__);                                                 \
+    } while (0)
+
+struct DevMem {
+    void* p = nullptr;
+    size_t bytes = 0;
+    ~DevMem() { if (p) (void)hipFree(p); }
+    int ensure(size_t n)
+    {
+        if (n <= bytes) return KH_OK;
+        if (p) { (void)hipFree(p); p = nullptr; bytes = 0; }
+        HIPCHK(hipMalloc(&p, n));
+        bytes = n;
+        return KH_OK;
+    }
+    template <class T> T* as() const { return static_cast<T*>(p); }
+};
+
+// page-locked host staging: one DMA per direction instead of one driver-staged copy per argument
+struct PinMem {
+    void* p = nullptr;
+    size_t bytes = 0;
+    ~PinMem() { if (p) (void)hipHostFree(p); }
+    int ensure(size_t n)
+    {
+        if (n <= bytes) return KH_OK;
+        if (p) { (void)hipHostFree(p); p = nullptr; bytes = 0; }
+        n += n / 2;                              // action counts vary from call to call
+        HIPCHK(hipHostMalloc(&p, n, hipHostMallocDefault));
+        bytes = n;
+        return KH_OK;
+    }
+    char* at(size_t off) const { return static_cast<char*>(p) + off; }
+};
+
+// One immutable, device-resident parameter set.  kh_load_weights builds a new one and swaps
+// the engine's shared_ptr; calls in flight keep the old set alive until they finish.
+struct Weights {
+    int generation = 0;
+    int64_t bn_batches = 0;              // BatchNorm num_batches_tracked of the reference (kh_bn_batches): carried, never computed with
+    std::vector<float> blob;             // host copy (kh_clone)
+    DevMem simple;                       // fp32 [tap][ci][co] + scale/shift per layer
+    std::vector<kh::SimpleLayer> layers; // stem, 2R tower convs, policyconv, policyconv2, valueconv
+    const float *fcw = nullptr, *fcb = nullptr;
+    // whole-network MFMA kernel (tower8_mfma.hip): packed fragment stream + folded parameters
+    DevMem tw_stream, tw_par, tw_fc4;
+    int tw_nchunks = 0, tw_npar = 0, tw_FP = 0;
+    bool tw_ok = false;
+    std::string tw_why;
+    // per-layer MFMA path for wide nets (layers_mfma.hip)
+    DevMem ly_w, ly_shift, ly_misc;      // ly_misc: vw[CP], fcw[256*64], fcb[256], fc4[16][256][4]
+    DevMem ly_w4;                        // 3x3 layers once more, packed for conv4_mfma_kernel
+    DevMem ly_w2b;                       // stem + tower packed for tower256_kernel (256-channel blocks)
+    bool ly_w2b_ok = false;
+    DevMem ly_wh;                        // policyconv + policyconv2 packed for policy_head4_kernel
+    bool ly_wh_ok = false;
+    std::vector<size_t> ly_w_off, ly_shift_off, ly_w4_off;
+    int ly_FP = 0, ly_CP = 0;
+    float ly_vshift = 0.0f;
+    bool ly_ok = false;
+};
+
+// ------------------------------------------------------------------------------- slots
+// Per-call workspace: stream + device scratch.  kh_infer may be called concurrently from many
+// host threads on one engine (nn.cpp:166 takes a shared lock); each call owns one slot.
+struct Slot {
+    hipStream_t stream = nullptr;
+    int cap = 0;                 // boards the scratch is sized for
+    DevMem in, x, t, u, ph, logits, policy, v64, vfull, flags, boards, planes, offs, acts, priors, actin, xchg;
+    DevMem pack_in, pack_out;    // legal-move host path: arguments / results packed for one copy each way
+    PinMem hin, hout;
+    hipStream_t stream2 = nullptr;   // registered caller buffers: chunks alternate between the two streams
+    bool busy = false;
+    bool flags_clean = false;    // device NaN flags known to be zero
+    // device-pointer API: the scratch above is shared by every caller stream, so a call on another stream
+    // than the previous one first waits for that call's last kernel (event recorded behind it)
+    hipEvent_t scratch_done = nullptr;
+    hipStream_t scratch_stream = nullptr;
+    bool scratch_pending = false;
+};
+
+struct TrainCache;      // kh_train's workspace (kh_api.hip)
+struct Queue;           // the submit / wait queue (queue.hip)
+
+}  // namespace kh
+
+struct kh_engine {
+    kh_config cfg;
+    int num_cus = 256;
+    bool f32_simple = false;     // KAMI_F32_SIMPLE=1: dtype f32 always runs forward_simple.hip
+    int small_max = 128;         // kh_infer up to this batch AND up to 768 KB of planes takes the zero-copy path
+                                 // (KAMI_SMALL_MAX; 0: never): measured 1.6x per thread at batch 16, even at 2 MB of planes
+    std::mutex wmu;
+    std::shared_ptr<kh::Weights> weights;
+    std::mutex smu;
+    std::condition_variable scv;
+    std::vector<std::unique_ptr<kh::Slot>> slots;
+    std::unique_ptr<kh::Slot> devslot;           // scratch for the device-pointer API
+    std::mutex dmu;
+    kh::Queue* co = nullptr;          // submit / wait queue (created on first use)
+    std::atomic<kh::Queue*> co_ready{ nullptr };     // the same pointer once the dispatcher runs: submitters skip co_mu
+    std::atomic<bool> has_weights{ false };
+    std::mutex co_mu;
+    std::atomic<int> small_calls{ 0 };       // synchronous small-batch calls currently inside the engine
+    std::atomic<int> co_target{ 0 }, co_wait_us{ 0 }, co_callers{ 0 };
+    // kh_train's workspace, staging, stream and recorded step: kept from call to call (selfplay.cpp:266 trains again and
+    // again with the same batch size and learning rate; allocating 0.1-2 GB and instantiating a ~270-node graph per
+    // call cost more than a dozen SGD steps)
+    std::mutex train_mu;
+    kh::TrainCache* train = nullptr;
+    // caller buffers registered with kh_pin_buffer: [base, base + bytes)
+    std::mutex pin_mu;
+    std::vector<std::pair<const char*, size_t>> pinned;
+};
+
+namespace kh {
+
+// ---- kh_api.hip
+int set_device(kh_engine* e);
+int slot_ensure(kh_engine* e, Slot& s, int batch, bool host_io);
+std::shared_ptr<Weights> current_weights(kh_engine* e);
+
+// The forward pass on device buffers, launched on `st`.  lg: the whole-network kernel's legal-move mode (TowerArgs::lg_*).
+struct LegalDev { const int32_t* offsets; const int32_t* actions; float* priors; float* values; int* flags; };
+int forward_tower(kh_engine* e, const Weights& W, Slot& s, hipStream_t st, const float* d_in, int B,
+                  float* d_policy, float* d_vfull, float* d_logits_out, const kh_board* d_boards = nullptr,
+                  const LegalDev* lg = nullptr);
+int forward_dispatch(kh_engine* e, const Weights& W, Slot& s, hipStream_t st, const float* d_in, int B,
+                     float* d_policy, float* d_vfull, float* d_logits_out);
+bool fused_ingest(const kh_engine* e, const Weights& W);
+
+// One host-buffer inference call (kh_infer*, the queue's synchronous kinds): planes [batch][8][8][F] or compact records
+// in; the outputs the caller wants (null: not wanted), `value` by value_mode, `legal` the priors of the legal actions.
+struct LegalIO { const int32_t* offsets; const int32_t* actions; float* priors; };
+struct HostCall {
+    const float* input = nullptr;
+    const kh_board* boards = nullptr;
+    int batch = 0;
+    float *policy = nullptr, *value = nullptr, *value_full = nullptr, *logits = nullptr;
+    const LegalIO* legal = nullptr;
+};
+int infer_host(kh_engine* e, const HostCall& c);
+
+int nan_status(Slot& s, const int* flags);                  // KH_ERR_NAN_* for the NaN flags a forward left
+int check_offsets(const int32_t* offsets, int batch);       // action_offsets start at 0 and never decrease
+int check_records(const kh_engine* e, const char* who);     // compact records need features == 30
+
+// ---- weights.hip: builds a parameter set from the blob and makes it the engine's current one
+int load_weights_impl(kh_engine* e, const float* blob, size_t nfloats, int generation, int64_t bn_batches,
+                      std::shared_ptr<Weights>* installed);
+
+// ---- queue.hip: the ABI's queue entry points
+int co_submit(kh_engine* e, int kind, const kh_board* boards, const float* planes, int batch, const int32_t* offsets,
+              const int32_t* actions, float* priors, float* value, float* policy, int64_t* ticket);
+int co_wait(kh_engine* e, int64_t ticket);
+int co_try_wait(kh_engine* e, int64_t ticket, int* done);
+int co_set_coalesce(kh_engine* e, int target_batch, int max_wait_us);
+int co_set_callers(kh_engine* e, int callers);
+int co_stats(kh_engine* e, int64_t* launches, int64_t* rows);
+int co_encode_infer_legal(kh_engine* e, const kh_board* boards, int batch, const int32_t* action_offsets,
+                          const int32_t* actions, float* priors, float* value);
+void co_destroy(kh_engine* e);
+
+}  // namespace kh

@@ -25,6 +25,8 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include "blob_layout.h"
+
 namespace kh_archive {
 
 // a request the format cannot hold (zip64 size, bad shape): the caller's fault, not the file system's
@@ -135,41 +137,16 @@ inline void write_zip(FILE* f, const std::vector<Record>& recs)
 
 }  // namespace wdetail
 
-// The kami network (nn.cpp:20-23,45-56) from a blob in the canonical order of include/kami_hip.h (conv1, batchnorm1,
-// residual blocks, policyconv, pbatchnorm, policyconv2, valueconv, vbatchnorm, valuefc), written as the reference's
-// module tree: attributes in its registration order, every BatchNorm with its int64 num_batches_tracked = bn_batches,
-// then `generation`.  The file appears at `path` only once complete (temporary file in the same directory + rename).
-// Throws Unsupported for an impossible shape or a zip64-sized archive, std::runtime_error on an I/O failure.
-inline void write_checkpoint(const std::string& path, int F, int C, int R, int64_t generation, int64_t bn_batches,
-                             const float* blob, size_t nfloats, int policy_mid = 128, int policy_planes = 73, int value_width = 256)
+// The kami network (nn.cpp:20-23,45-56) from a blob in the canonical order of include/kami_hip.h (`specs`: its
+// blob_layout.h list for R residual blocks), written as the reference's module tree: attributes in its registration order,
+// every BatchNorm with its int64 num_batches_tracked = bn_batches, then `generation`.  The file appears at `path` only
+// once complete (temporary file in the same directory + rename).
+// Throws Unsupported for a zip64-sized archive, std::runtime_error on an I/O failure.
+inline void write_checkpoint(const std::string& path, int R, int64_t generation, int64_t bn_batches, const float* blob,
+                             const std::vector<kh_blob::Tensor>& specs)
 {
     using namespace wdetail;
-    if (F < 1 || F > 4096 || C < 1 || C > 1024 || R < 0 || R > 256) throw Unsupported("impossible network shape");
-    // blob offsets of every tensor, in blob order
-    struct T { std::string name; std::vector<int64_t> shape; size_t at; };
-    std::vector<T> specs;
-    size_t at = 0;
-    auto tensor = [&](const std::string& name, std::vector<int64_t> shape) {
-        size_t n = 1;
-        for (int64_t s : shape) n *= (size_t)s;
-        specs.push_back({ name, std::move(shape), at });
-        at += n;
-    };
-    auto convbn = [&](const std::string& conv, const std::string& bn, int co, int ci, int k) {
-        tensor(conv + ".weight", { co, ci, k, k }); tensor(conv + ".bias", { co });
-        for (const char* s : { ".weight", ".bias", ".running_mean", ".running_var" }) tensor(bn + s, { co });
-    };
-    convbn("conv1", "batchnorm1", C, F, 3);
-    for (int i = 0; i < R; ++i) {
-        const std::string r = "residual" + std::to_string(i);
-        convbn(r + ".conv1", r + ".batchnorm1", C, C, 3);
-        convbn(r + ".conv2", r + ".batchnorm2", C, C, 3);
-    }
-    convbn("policyconv", "pbatchnorm", policy_mid, C, 1);
-    tensor("policyconv2.weight", { policy_planes, policy_mid, 1, 1 }); tensor("policyconv2.bias", { policy_planes });
-    convbn("valueconv", "vbatchnorm", 1, C, 1);
-    tensor("valuefc.weight", { value_width, 64 }); tensor("valuefc.bias", { value_width });
-    if (at != nfloats) throw Unsupported("blob has " + std::to_string(nfloats) + " floats, the network has " + std::to_string(at));
+    using T = kh_blob::Tensor;
     auto find = [&](const std::string& name) -> const T& {
         for (auto& t : specs) if (t.name == name) return t;
         throw std::logic_error("no tensor " + name);
@@ -186,11 +163,9 @@ inline void write_checkpoint(const std::string& path, int F, int C, int R, int64
     auto param = [&](const std::string& name, const char* leaf, bool is_param) {
         const T& t = find(name + "." + leaf);
         keys.push_back(std::to_string(keys.size()));
-        int64_t numel = 1;
-        for (int64_t s : t.shape) numel *= s;
         pk.str(leaf);
-        pk.tensor("FloatStorage", keys.back(), numel, t.shape, is_param);
-        recs.push_back({ root + "data/" + keys.back(), reinterpret_cast<const uint8_t*>(blob + t.at), (size_t)numel * 4 });
+        pk.tensor("FloatStorage", keys.back(), (int64_t)t.n, t.shape, is_param);
+        recs.push_back({ root + "data/" + keys.back(), reinterpret_cast<const uint8_t*>(blob + t.at), t.n * 4 });
     };
     auto conv = [&](const std::string& attr, const std::string& name, const char* cls) {
         pk.str(attr); pk.begin_object(cls);

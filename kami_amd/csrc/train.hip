@@ -14,6 +14,7 @@
 // layout (the BatchNorm running-statistics slots stay zero), so SGD is one axpy over the blob.
 // Activations are [B][64][C] fp32 channels-last like forward_simple.hip.
 #include "kh_internal.h"
+#include "blob_layout.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -554,23 +555,23 @@ static TrainNet layout(int F, int C, int R)
 {
     TrainNet n;
     n.F = F; n.C = C; n.R = R;
-    size_t o = 0;
-    auto convbn = [&](int Ci, int Co, int T) {
+    const std::vector<kh_blob::Tensor> L = kh_blob::layout(F, C, R);
+    size_t i = 0;
+    auto take = [&] { return L[i++].at; };
+    auto convbn = [&] {
         ConvBNOff c;
-        c.Ci = Ci; c.Co = Co; c.T = T;
-        c.w = o; o += (size_t)Co * Ci * T;
-        c.b = o; o += Co; c.g = o; o += Co; c.be = o; o += Co; c.rm = o; o += Co; c.rv = o; o += Co;
+        const std::vector<int64_t>& s = L[i].shape;
+        c.Co = (int)s[0]; c.Ci = (int)s[1]; c.T = (int)(s[2] * s[3]);
+        c.w = take(); c.b = take(); c.g = take(); c.be = take(); c.rm = take(); c.rv = take();
         return c;
     };
-    n.stem = convbn(F, C, 9);
-    for (int i = 0; i < 2 * R; ++i) n.res.push_back(convbn(C, C, 9));
-    n.pconv = convbn(C, KH_POLICY_MID, 1);
-    n.p2w = o; o += (size_t)KH_POLICY_PLANES * KH_POLICY_MID;
-    n.p2b = o; o += KH_POLICY_PLANES;
-    n.vconv = convbn(C, 1, 1);
-    n.fcw = o; o += (size_t)KH_VALUE_WIDTH * 64;
-    n.fcb = o; o += KH_VALUE_WIDTH;
-    n.total = o;
+    n.stem = convbn();
+    for (int r = 0; r < 2 * R; ++r) n.res.push_back(convbn());
+    n.pconv = convbn();
+    n.p2w = take(); n.p2b = take();
+    n.vconv = convbn();
+    n.fcw = take(); n.fcb = take();
+    n.total = kh_blob::total(L);
     return n;
 }
 

@@ -6,7 +6,7 @@
 set -e
 cd "$(dirname "$0")/../kami_amd/csrc"
 SRCS=${VARIANT_SRCS:-"tower8_mfma"}
-ALL="kh_api encode forward_simple tower_mfma tower8_mfma layers_mfma train"
+ALL="kh_api weights queue encode forward_simple tower_mfma tower8_mfma layers_mfma train"
 RT=$(python3 -c 'import os,torch;print(os.path.join(os.path.dirname(torch.__file__),"lib"))' 2>/dev/null || echo /opt/rocm/lib)
 for spec in "$@"; do
   name="${spec%%:*}"; flags="${spec#*:}"
