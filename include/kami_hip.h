@@ -131,6 +131,42 @@ int  kh_train(kh_engine* e, const float* inputs, const float* obs_p, const float
  * persist).  No engine needed: what a restatement of a multi-batch run has to follow. */
 int  kh_train_order(int trajectories, int epochs, int32_t* order);
 
+/* ---- compact replay records as the trainer's input ------------------------------------------------------------
+ * One finished-game position as self-play produces it (selfplay.cpp:176-184, MCTS::snapshot mcts.h:341-348): the board
+ * Env::observe reads, the visit shares of up to KH_MAX_RECORD_ACTIONS moves and the value target.  664 bytes where
+ * replaybuffer.h:20-22 holds OBSIZE + PSIZE + 1 floats (26 372 bytes). */
+#define KH_MAX_RECORD_ACTIONS 96
+typedef struct kh_record {
+    kh_board board;             /* the observation, compact                                                    */
+    float    value;             /* training target                                                             */
+    int32_t  nact;              /* 0 .. KH_MAX_RECORD_ACTIONS                                                   */
+    int16_t  actions[KH_MAX_RECORD_ACTIONS];   /* action codes in [0, 4672), pairwise distinct                 */
+    float    visits[KH_MAX_RECORD_ACTIONS];    /* visit share of actions[k]                                    */
+} kh_record;
+
+/* What makes a record usable as a training sample: 0 <= nact <= 96, actions[k] in [0, 4672) for k < nact, and those
+ * actions pairwise distinct.  Visit shares, value and board bits are not judged (the dense arrays would carry the same
+ * numbers).  On a violation: KH_ERR_INVALID, *bad_index (nullable) = the first offending record, and a message that
+ * names the record and the rule.  No engine and no GPU needed. */
+int  kh_records_validate(const kh_record* rec, int n, int* bad_index);
+
+/* The dense arrays kh_train takes, from records: planes[i] = what kh_encode gives for board i (bit-exact), obs_p[i] =
+ * zeros with obs_p[i][actions[k]] = visits[k] for k < nact, obs_v[i] = value.  Host buffers; each output is nullable.
+ * Expanded on the device in chunks.  Records are validated first; requires cfg.features == 30. */
+int  kh_expand_records(kh_engine* e, const kh_record* rec, int n,
+                       float* planes /*[n][8][8][30]*/, float* obs_p /*[n][4672]*/, float* obs_v /*[n]*/);
+
+/* kh_train on records: for valid records exactly kh_train on the three arrays kh_expand_records returns — the same
+ * sample order, the same rows behind a short batch, the same arithmetic, so parameters, BatchNorm statistics, both
+ * losses, kh_generation and kh_bn_batches match bit for bit, and so do status and message of a failed call ("training
+ * loss is NaN (epoch %d, batch %d)", the two detect_anomaly output messages; "training input ind ... contains NaN"
+ * cannot occur, because the encoder emits no NaN).  A failed call leaves the parameters as they were.  The records and
+ * the sample order are uploaded once (n x 664 bytes); every batch is expanded on the device into the buffers the
+ * training step reads, and the host synchronises once per call instead of once per batch.  Same argument checks as
+ * kh_train; records are validated before anything is uploaded; requires cfg.features == 30. */
+int  kh_train_records(kh_engine* e, const kh_record* rec, int n,
+                      const kh_train_config* cfg, float* first_loss, float* last_loss);
+
 /* NN::read nn.cpp:204-222: parse a checkpoint file without an engine.  Two containers are understood:
  * the reference's own — the libtorch archive NN::write leaves (nn.cpp:189-202: module.save + the
  * "generation" IValue), read here with a zip walk and a pickle stack machine (csrc/torch_archive.h; no

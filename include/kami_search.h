@@ -75,15 +75,9 @@ typedef struct ks_pool_stats {
     double  engine_seconds;     /* time the workers spent inside kh_encode_infer_legal, summed over workers     */
 } ks_pool_stats;
 
-/* one finished-game position: replaybuffer.h:20-22 holds OBSIZE + PSIZE + 1 floats (26 372 B) for this */
-#define KS_MAX_RECORD_ACTIONS 96
-typedef struct ks_record {
-    kh_board board;             /* the observation, compact                                                    */
-    float    value;             /* training target (selfplay.cpp:176-184)                                      */
-    int32_t  nact;
-    int16_t  actions[KS_MAX_RECORD_ACTIONS];
-    float    visits[KS_MAX_RECORD_ACTIONS];   /* MCTS::snapshot, sparse (mcts.h:341-348)                       */
-} ks_record;
+/* one finished-game position: kh_record (kami_hip.h), the form the trainer takes as well */
+#define KS_MAX_RECORD_ACTIONS KH_MAX_RECORD_ACTIONS
+typedef kh_record ks_record;
 
 typedef struct ks_pool ks_pool;
 int  ks_pool_create(kh_engine* engine, const ks_pool_config* cfg, ks_pool** out);
@@ -98,6 +92,20 @@ int  ks_pool_publish_weights(ks_pool* p, const float* blob, size_t nfloats, int 
 int  ks_pool_run(ks_pool* p, int64_t min_evals, double max_seconds, ks_pool_stats* stats);
 int64_t ks_pool_drain_records(ks_pool* p, ks_record* out, int64_t cap);
 void ks_pool_destroy(ks_pool* p);
+
+/* ---- compact replay ring (kami/replaybuffer.h:10-92 over ks_record) ----------------------------------------- */
+/* A fixed ring of `capacity` records under one mutex.  count = records ever added (it keeps counting past the capacity,
+ * the oldest slot is overwritten); select = n uniform draws with replacement over the WHOLE ring, from the ring's own
+ * generator seeded with `seed`; a never-written slot is the all-zero record (empty board, nact 0, value 0), which is a
+ * valid training sample.  What ks_ring_select returns is what kh_train_records takes. */
+typedef struct ks_ring ks_ring;
+ks_ring* ks_ring_new(int capacity, uint64_t seed);
+void     ks_ring_free(ks_ring* r);
+int      ks_ring_add(ks_ring* r, const ks_record* records, int64_t n);
+int64_t  ks_ring_count(ks_ring* r);
+int      ks_ring_size(ks_ring* r);
+void     ks_ring_clear(ks_ring* r);
+int      ks_ring_select(ks_ring* r, int n, ks_record* out_records);
 
 const char* ks_last_error(void);
 

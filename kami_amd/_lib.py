@@ -30,6 +30,26 @@ BOARD_DTYPE = np.dtype([("piece_occ", "<u8", (6,)), ("color_occ", "<u8", (2,)),
                         ("ctm", "u1"), ("castle_rights", "u1"), ("pad", "u1", (6,))])
 assert BOARD_DTYPE.itemsize == 80
 
+class Board(C.Structure):
+    """kh_board; same bytes as BOARD_DTYPE."""
+    _fields_ = [("piece_occ", C.c_uint64 * 6), ("color_occ", C.c_uint64 * 2), ("ply", C.c_int32), ("halfmove_clock", C.c_int32),
+                ("ctm", C.c_uint8), ("castle_rights", C.c_uint8), ("pad", C.c_uint8 * 6)]
+
+
+MAX_RECORD_ACTIONS = 96
+
+
+class Record(C.Structure):
+    """kh_record (664 bytes): one finished-game position as self-play produces it and kh_train_records consumes it."""
+    _fields_ = [("board", Board), ("value", C.c_float), ("nact", C.c_int32),
+                ("actions", C.c_int16 * MAX_RECORD_ACTIONS), ("visits", C.c_float * MAX_RECORD_ACTIONS)]
+
+
+# numpy view of kh_record
+RECORD_DTYPE = np.dtype([("board", BOARD_DTYPE), ("value", "<f4"), ("nact", "<i4"),
+                         ("actions", "<i2", (MAX_RECORD_ACTIONS,)), ("visits", "<f4", (MAX_RECORD_ACTIONS,))])
+assert C.sizeof(Board) == 80 and C.sizeof(Record) == 664 and RECORD_DTYPE.itemsize == 664
+
 # every symbol include/kami_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 class TrainConfig(C.Structure):
@@ -43,6 +63,9 @@ SYMBOLS = {
     "kh_load_weights": (C.c_int, [_P, _P, C.c_size_t, C.c_int]),
     "kh_train": (C.c_int, [_P, _P, _P, _P, C.c_int, C.POINTER(TrainConfig), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "kh_train_order": (C.c_int, [C.c_int, C.c_int, _P]),
+    "kh_records_validate": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    "kh_expand_records": (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
+    "kh_train_records": (C.c_int, [_P, _P, C.c_int, C.POINTER(TrainConfig), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "kh_checkpoint_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                      _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "kh_checkpoint_read_ex": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),

@@ -1,10 +1,12 @@
 // engine.h — the engine's host-side state and the declarations its translation units share: kh_api.hip (C ABI, slots,
-// forward wrappers, host and device I/O, kh_train, checkpoints), weights.hip (parameter sets) and queue.hip (the
-// coalescing queue).  Not part of the public boundary (that is include/kami_hip.h).
+// forward wrappers, host and device I/O, kh_train, checkpoints), weights.hip (parameter sets), queue.hip (the
+// coalescing queue) and train_ingest.hip (kh_train_records, kh_expand_records).  Not part of the public boundary (that
+// is include/kami_hip.h).
 #pragma once
 #include "kh_internal.h"
 
 #include <atomic>
+#include <chrono>
 #include <condition_variable>
 #include <memory>
 #include <mutex>
@@ -103,8 +105,36 @@ struct Slot {
     bool scratch_pending = false;
 };
 
-struct TrainCache;      // kh_train's workspace (kh_api.hip)
 struct Queue;           // the submit / wait queue (queue.hip)
+
+// The trainer's workspace, shared by kh_train (kh_api.hip) and kh_train_records (train_ingest.hip): both write a batch
+// into dx / dp / dv and run the same recorded step on it, so alternating them on one engine re-records nothing.
+struct TrainCache {
+    DevMem params, grads, work, dx, dp, dv, dloss;
+    DevMem rec, order;                          // kh_train_records: the call's records (RecordBlock layout) and sample order
+    PinMem pin, pin_params;                     // batch staging; the parameter blob on its way up (a pageable source made the
+                                                // upload take 0.1 ms or 10-27 ms from call to call: the runtime pins it on the fly)
+    PinMem pin_rec, pin_loss;                   // kh_train_records: records + order on their way up; one dloss slot per step
+    std::weak_ptr<Weights> on_device;           // the weights whose blob `params` holds right now (the previous call's result):
+                                                // training them again needs no upload at all
+    hipStream_t st = nullptr;
+    hipGraph_t g = nullptr;
+    hipGraphExec_t x = nullptr;
+    int B = 0;
+    float lr = 0.0f;
+    bool valu = false, graph_tried = false;
+    void drop_graph()
+    {
+        if (x) (void)hipGraphExecDestroy(x);
+        if (g) (void)hipGraphDestroy(g);
+        x = nullptr; g = nullptr; graph_tried = false;
+    }
+    ~TrainCache()
+    {
+        drop_graph();
+        if (st) (void)hipStreamDestroy(st);
+    }
+};
 
 }  // namespace kh
 
@@ -139,6 +169,32 @@ struct kh_engine {
 
 namespace kh {
 
+// a call's lease on one of the engine's workspace slots (waits for a free one once MAX_SLOTS exist)
+constexpr int MAX_SLOTS = 32;
+struct SlotLease {
+    kh_engine* e;
+    Slot* s = nullptr;
+    explicit SlotLease(kh_engine* e_) : e(e_)
+    {
+        std::unique_lock<std::mutex> lk(e->smu);
+        for (;;) {
+            for (auto& p : e->slots)
+                if (!p->busy) { s = p.get(); break; }
+            if (!s && (int)e->slots.size() < MAX_SLOTS) {
+                e->slots.emplace_back(new Slot());
+                s = e->slots.back().get();
+            }
+            if (s) { s->busy = true; return; }
+            e->scv.wait(lk);
+        }
+    }
+    ~SlotLease()
+    {
+        { std::lock_guard<std::mutex> lk(e->smu); s->busy = false; }
+        e->scv.notify_one();
+    }
+};
+
 // ---- kh_api.hip
 int set_device(kh_engine* e);
 int slot_ensure(kh_engine* e, Slot& s, int batch, bool host_io);
@@ -168,6 +224,39 @@ int infer_host(kh_engine* e, const HostCall& c);
 int nan_status(Slot& s, const int* flags);                  // KH_ERR_NAN_* for the NaN flags a forward left
 int check_offsets(const int32_t* offsets, int batch);       // action_offsets start at 0 and never decrease
 int check_records(const kh_engine* e, const char* who);     // compact records need features == 30
+
+// ---- kh_api.hip: the parts of a training call that do not depend on where the batches come from
+struct TrainCall {
+    std::shared_ptr<Weights> W;                                  // the set being trained
+    std::unique_ptr<TrainNet, void (*)(TrainNet*)> net{ nullptr, train_layout_free };
+    std::unique_lock<std::mutex> lock;                           // e->train_mu, held until the call returns
+    TrainCache* tc = nullptr;
+    hipStream_t st = nullptr;
+    size_t nfl = 0;
+    int B = 0;
+    std::chrono::steady_clock::time_point t_call, t_bufs, t_up, t_setup, t_steps;   // KAMI_TRAIN_TRACE
+};
+// weights, lock, workspace (drops the recorded step when what it holds changed), stream, parameters on the device
+int train_begin(kh_engine* e, const kh_train_config* cfg, const char* who, TrainCall& c);
+// one SGD step on dx / dp / dv -> dloss: the recorded graph (recorded at the first step) or plain launches
+int train_launch_step(TrainCall& c, float lr);
+// nn.cpp:337-341 and the loss of one step from its dloss block ([2B] rows + the two NaN flags), as kh_train reports them
+int train_step_result(const float* loss_rows, int B, bool detect_anomaly, int epoch, int batch, float* loss);
+// parameters back, installed as generation + 1 with the BatchNorm counter advanced
+int train_finish(kh_engine* e, TrainCall& c, int trajectories, int epochs);
+
+// ---- train_ingest.hip: compact records (kh_record) as the trainer's input
+// Records re-laid as arrays in one block, every array 16-byte aligned (sizeof(kh_record) is not a multiple of 16, and
+// encode_square() fetches a kh_board with 16-byte loads): kh_board[n], value[n], nact[n], actions[n][96], visits[n][96].
+struct RecordBlock {
+    size_t boards, value, nact, actions, visits, bytes;          // byte offsets
+    explicit RecordBlock(size_t n);
+    void pack(char* dst, const kh_record* rec, size_t n) const;
+};
+// rows [0, count) of dx / dp / dv from records order[base + r] (order == nullptr: records base + r)
+void launch_expand_records(const char* d_block, const RecordBlock& lay, const int32_t* d_order, int base, int count,
+                           float* dx, float* dp, float* dv, hipStream_t s);
+int records_check(const kh_record* rec, int n, int* bad_index);
 
 // ---- weights.hip: builds a parameter set from the blob and makes it the engine's current one
 int load_weights_impl(kh_engine* e, const float* blob, size_t nfloats, int generation, int64_t bn_batches,

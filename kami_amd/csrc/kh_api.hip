@@ -1,6 +1,7 @@
 // kh_api.hip — the C ABI of libkamihip.so (include/kami_hip.h): engine object, workspace slots, forward wrappers,
 // host-buffer and device-buffer entry points, kh_train's host loop and checkpoints.  Parameter sets are built in
-// weights.hip, the coalescing queue lives in queue.hip (engine.h: what the three share).
+// weights.hip, the coalescing queue lives in queue.hip, training from compact records in train_ingest.hip (engine.h:
+// what they share).
 //
 // Boundary being replaced: class kami::NN (kami/nn/nn.h:40-73, kami/nn/nn.cpp:107-222) and
 // Env::observe (kami/env.h:202-262).  There is no CPU fallback anywhere in this library:
@@ -34,33 +35,6 @@ int fail(int code, const char* fmt, ...)
     return code;
 }
 
-struct TrainCache {
-    DevMem params, grads, work, dx, dp, dv, dloss;
-    PinMem pin, pin_params;                     // batch staging; the parameter blob on its way up (a pageable source made the
-                                                // upload take 0.1 ms or 10-27 ms from call to call: the runtime pins it on the fly)
-    std::weak_ptr<Weights> on_device;           // the weights whose blob `params` holds right now (the previous call's result):
-                                                // training them again needs no upload at all
-    hipStream_t st = nullptr;
-    hipGraph_t g = nullptr;
-    hipGraphExec_t x = nullptr;
-    int B = 0;
-    float lr = 0.0f;
-    bool valu = false, graph_tried = false;
-    void drop_graph()
-    {
-        if (x) (void)hipGraphExecDestroy(x);
-        if (g) (void)hipGraphDestroy(g);
-        x = nullptr; g = nullptr; graph_tried = false;
-    }
-    ~TrainCache()
-    {
-        drop_graph();
-        if (st) (void)hipStreamDestroy(st);
-    }
-};
-
-constexpr int MAX_SLOTS = 32;
-
 int set_device(kh_engine* e) { HIPCHK(hipSetDevice(e->cfg.device)); return KH_OK; }
 
 int slot_ensure(kh_engine* e, Slot& s, int batch, bool host_io)
@@ -87,30 +61,6 @@ int slot_ensure(kh_engine* e, Slot& s, int batch, bool host_io)
     s.cap = batch;
     return KH_OK;
 }
-
-struct SlotLease {
-    kh_engine* e;
-    Slot* s = nullptr;
-    explicit SlotLease(kh_engine* e_) : e(e_)
-    {
-        std::unique_lock<std::mutex> lk(e->smu);
-        for (;;) {
-            for (auto& p : e->slots)
-                if (!p->busy) { s = p.get(); break; }
-            if (!s && (int)e->slots.size() < MAX_SLOTS) {
-                e->slots.emplace_back(new Slot());
-                s = e->slots.back().get();
-            }
-            if (s) { s->busy = true; return; }
-            e->scv.wait(lk);
-        }
-    }
-    ~SlotLease()
-    {
-        { std::lock_guard<std::mutex> lk(e->smu); s->busy = false; }
-        e->scv.notify_one();
-    }
-};
 
 std::shared_ptr<Weights> current_weights(kh_engine* e)
 {
@@ -545,6 +495,118 @@ int infer_host(kh_engine* e, const HostCall& c)
     return infer_staged(e, *W, s, c);
 }
 
+// ------------------------------------------------------------------------------- training calls
+int train_begin(kh_engine* e, const kh_train_config* cfg, const char* who, TrainCall& c)
+{
+    c.t_call = std::chrono::steady_clock::now();
+    c.W = current_weights(e);
+    if (!c.W) return fail(KH_ERR_NO_WEIGHTS, "%s before kh_load_weights", who);
+    int rc = set_device(e);
+    if (rc) return rc;
+    const int F = e->cfg.features, C = e->cfg.filters, R = e->cfg.residuals, B = cfg->batch;
+    c.net.reset(kh::train_layout_new(F, C, R));
+    c.nfl = c.W->blob.size();
+    c.B = B;
+    const size_t nfl = c.nfl;
+    c.lock = std::unique_lock<std::mutex>(e->train_mu);       // one trainer per engine at a time (the reference: exclusive lock, nn.cpp:226)
+    if (!e->train) e->train = new TrainCache();
+    TrainCache& tc = *e->train;
+    c.tc = &tc;
+    DevMem &params = tc.params, &grads = tc.grads, &work = tc.work, &dx = tc.dx, &dp = tc.dp, &dv = tc.dv, &dloss = tc.dloss;
+    const bool valu_now = getenv("KAMI_TRAIN_VALU") && atoi(getenv("KAMI_TRAIN_VALU")) != 0;
+    {
+        const void* before[3] = { params.p, work.p, dx.p };
+        if ((rc = params.ensure(nfl * 4)) || (rc = grads.ensure(nfl * 4)) || (rc = work.ensure(kh::train_workspace_floats(F, C, R, B) * 4)) ||
+            (rc = dx.ensure((size_t)B * 64 * F * 4)) || (rc = dp.ensure((size_t)B * KH_PSIZE * 4)) || (rc = dv.ensure((size_t)B * 4)) ||
+            (rc = dloss.ensure((size_t)B * 2 * 4 + 8)))
+            return rc;
+        // the recorded step holds buffer addresses, the batch size, the learning rate and the kernel choice
+        if (before[0] != params.p || before[1] != work.p || before[2] != dx.p || tc.B != B || tc.lr != cfg->lr || tc.valu != valu_now) tc.drop_graph();
+        if (before[0] != params.p) tc.on_device.reset();
+        tc.B = B; tc.lr = cfg->lr; tc.valu = valu_now;
+    }
+    c.t_bufs = std::chrono::steady_clock::now();
+    if (!tc.st) HIPCHK(hipStreamCreateWithFlags(&tc.st, hipStreamNonBlocking));
+    c.st = tc.st;
+    if (tc.on_device.lock() != c.W) {
+        // through a page-locked block of the trainer's own (the blob is a std::vector)
+        if (tc.pin_params.ensure(nfl * 4)) return KH_ERR_HIP;
+        memcpy(tc.pin_params.p, c.W->blob.data(), nfl * 4);
+        HIPCHK(hipMemcpyAsync(params.p, tc.pin_params.p, nfl * 4, hipMemcpyHostToDevice, c.st));
+    }                                            // else: `params` still holds exactly these weights — the previous call trained them
+    tc.on_device.reset();                        // (until this call has installed its result, `params` belongs to nobody)
+    c.t_up = std::chrono::steady_clock::now();
+    HIPCHK(kh::conv_f32_raw_prepare());          // function attributes are not stream work: set them before any capture
+    return KH_OK;
+}
+
+static const bool train_trace = getenv("KAMI_TRAIN_TRACE") != nullptr;
+
+// A step is ~120 small launches on fixed buffers: recorded once as a graph, replayed per batch (with the
+// tiled conv kernels the host's launch work, not the GPU, bounded a step).  Falls back to plain launches.
+int train_launch_step(TrainCall& c, float lr)
+{
+    TrainCache& tc = *c.tc;
+    const int B = c.B;
+    hipStream_t st = c.st;
+    const kh::StepBuffers sb{ tc.params.as<float>(), tc.grads.as<float>(), tc.work.as<float>() };
+    float *dx = tc.dx.as<float>(), *dp = tc.dp.as<float>(), *dv = tc.dv.as<float>(), *dloss = tc.dloss.as<float>();
+    static const bool no_graph = getenv("KAMI_TRAIN_NOGRAPH") != nullptr;
+    if (!tc.graph_tried && no_graph) tc.graph_tried = true;
+    if (!tc.graph_tried) {
+        tc.graph_tried = true;
+        if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+            const hipError_t ce = kh::train_step(*c.net, sb, dx, dp, dv, B, lr, dloss, st);
+            const hipError_t ee = hipStreamEndCapture(st, &tc.g);
+            if (ce != hipSuccess || ee != hipSuccess || hipGraphInstantiate(&tc.x, tc.g, nullptr, nullptr, 0) != hipSuccess) {
+                if (tc.x) { (void)hipGraphExecDestroy(tc.x); tc.x = nullptr; }
+                (void)hipGetLastError();
+            }
+            if (train_trace) fprintf(stderr, "[kami train] step recorded as a graph: %s\n", tc.x ? "yes" : "NO (plain launches)");
+        }
+    }
+    if (tc.x) HIPCHK(hipGraphLaunch(tc.x, st));
+    else HIPCHK(kh::train_step(*c.net, sb, dx, dp, dv, B, lr, dloss, st));
+    return KH_OK;
+}
+
+int train_step_result(const float* loss_rows, int B, bool detect_anomaly, int epoch, int batch, float* loss_out)
+{
+    if (detect_anomaly) {                                 // nn.cpp:337-341: the value output first, then the policy
+        const int* nf = reinterpret_cast<const int*>(loss_rows + 2 * B);
+        if (nf[1]) return fail(KH_ERR_NAN_VALUE, "forward value output contains NaN");
+        if (nf[0]) return fail(KH_ERR_NAN_POLICY, "forward policy output contains NaN");
+    }
+    float lp = 0.0f, lv = 0.0f;
+    for (int b = 0; b < B; ++b) { lp += loss_rows[b]; lv += loss_rows[B + b]; }
+    const float loss = lp + lv / (float)(B * KH_VALUE_WIDTH);
+    if (loss != loss) return fail(KH_ERR_NAN_POLICY, "training loss is NaN (epoch %d, batch %d)", epoch, batch);
+    *loss_out = loss;
+    return KH_OK;
+}
+
+int train_finish(kh_engine* e, TrainCall& c, int trajectories, int epochs)
+{
+    TrainCache& tc = *c.tc;
+    const size_t nfl = c.nfl;
+    std::vector<float> blob(nfl);
+    HIPCHK(hipMemcpy(blob.data(), tc.params.p, nfl * 4, hipMemcpyDeviceToHost));
+    const auto t_read = std::chrono::steady_clock::now();
+    std::shared_ptr<Weights> installed;
+    // every training-mode forward (one per batch, the short last one included: nn.cpp:264-301) counts once in each
+    // BatchNorm's num_batches_tracked
+    const int64_t forwards = (int64_t)epochs * ((trajectories + c.B - 1) / c.B);
+    const int lrc = load_weights_impl(e, blob.data(), nfl, c.W->generation + 1, c.W->bn_batches + forwards, &installed);  // nn.cpp:371 ++generation
+    if (lrc == KH_OK) tc.on_device = installed;
+    if (train_trace) {
+        auto ms = [](std::chrono::steady_clock::duration d) { return std::chrono::duration<double, std::milli>(d).count(); };
+        fprintf(stderr, "[kami train] call: set-up %.2f ms (buffers %.2f, parameters up %.2f, staging %.2f), steps %.2f ms, parameters back %.2f ms, "
+                "weights installed %.2f ms\n", ms(c.t_setup - c.t_call), ms(c.t_bufs - c.t_call), ms(c.t_up - c.t_bufs), ms(c.t_setup - c.t_up),
+                ms(c.t_steps - c.t_setup), ms(t_read - c.t_steps), ms(std::chrono::steady_clock::now() - t_read));
+    }
+    return lrc;
+}
+
 }  // namespace kh
 
 using namespace kh;
@@ -619,41 +681,13 @@ int kh_train(kh_engine* e, const float* inputs, const float* obs_p, const float*
 {
     if (!e || !inputs || !obs_p || !obs_v || !cfg) return fail(KH_ERR_INVALID, "null argument");
     if (trajectories < 1 || cfg->batch < 2 || cfg->epochs < 1) return fail(KH_ERR_INVALID, "trajectories >= 1, batch >= 2, epochs >= 1 required");
-    const auto t_call = std::chrono::steady_clock::now();
-    auto W = current_weights(e);
-    if (!W) return fail(KH_ERR_NO_WEIGHTS, "kh_train before kh_load_weights");
-    int rc = set_device(e);
+    TrainCall call;
+    int rc = train_begin(e, cfg, "kh_train", call);
     if (rc) return rc;
-    const int F = e->cfg.features, C = e->cfg.filters, R = e->cfg.residuals, B = cfg->batch;
-    std::unique_ptr<kh::TrainNet, void (*)(kh::TrainNet*)> net(kh::train_layout_new(F, C, R), kh::train_layout_free);
-    const size_t nfl = W->blob.size();
-    std::lock_guard<std::mutex> train_lock(e->train_mu);      // one trainer per engine at a time (the reference: exclusive lock, nn.cpp:226)
-    if (!e->train) e->train = new TrainCache();
-    TrainCache& tc = *e->train;
-    DevMem &params = tc.params, &grads = tc.grads, &work = tc.work, &dx = tc.dx, &dp = tc.dp, &dv = tc.dv, &dloss = tc.dloss;
-    const bool valu_now = getenv("KAMI_TRAIN_VALU") && atoi(getenv("KAMI_TRAIN_VALU")) != 0;
-    {
-        const void* before[3] = { params.p, work.p, dx.p };
-        if ((rc = params.ensure(nfl * 4)) || (rc = grads.ensure(nfl * 4)) || (rc = work.ensure(kh::train_workspace_floats(F, C, R, B) * 4)) ||
-            (rc = dx.ensure((size_t)B * 64 * F * 4)) || (rc = dp.ensure((size_t)B * KH_PSIZE * 4)) || (rc = dv.ensure((size_t)B * 4)) ||
-            (rc = dloss.ensure((size_t)B * 2 * 4 + 8)))
-            return rc;
-        // the recorded step holds buffer addresses, the batch size, the learning rate and the kernel choice
-        if (before[0] != params.p || before[1] != work.p || before[2] != dx.p || tc.B != B || tc.lr != cfg->lr || tc.valu != valu_now) tc.drop_graph();
-        if (before[0] != params.p) tc.on_device.reset();
-        tc.B = B; tc.lr = cfg->lr; tc.valu = valu_now;
-    }
-    const auto t_bufs = std::chrono::steady_clock::now();
-    if (!tc.st) HIPCHK(hipStreamCreateWithFlags(&tc.st, hipStreamNonBlocking));
-    hipStream_t st = tc.st;
-    if (tc.on_device.lock() != W) {
-        // through a page-locked block of the trainer's own (the blob is a std::vector)
-        if (tc.pin_params.ensure(nfl * 4)) return KH_ERR_HIP;
-        memcpy(tc.pin_params.p, W->blob.data(), nfl * 4);
-        HIPCHK(hipMemcpyAsync(params.p, tc.pin_params.p, nfl * 4, hipMemcpyHostToDevice, st));
-    }                                            // else: `params` still holds exactly these weights — the previous call trained them
-    tc.on_device.reset();                        // (until this call has installed its result, `params` belongs to nobody)
-    const auto t_up = std::chrono::steady_clock::now();
+    TrainCache& tc = *call.tc;
+    DevMem &dx = tc.dx, &dp = tc.dp, &dv = tc.dv, &dloss = tc.dloss;
+    hipStream_t st = call.st;
+    const int F = e->cfg.features, B = cfg->batch;
 
     // nn.cpp:245-262: one engine for the whole call, one shuffle per epoch; staging rows persist
     std::vector<int> picker((size_t)trajectories);
@@ -670,14 +704,7 @@ int kh_train(kh_engine* e, const float* inputs, const float* obs_p, const float*
     float* loss_rows = next_value + B;
     memset(pin.p, 0, (n_in + n_p + (size_t)B + (size_t)B * 2 + 2) * 4);
     float firstloss = 0.0f, lastloss = 0.0f;
-    const kh::StepBuffers sb{ params.as<float>(), grads.as<float>(), work.as<float>() };
-    // A step is ~120 small launches on fixed buffers: recorded once as a graph, replayed per batch (with the
-    // tiled conv kernels the host's launch work, not the GPU, bounded a step).  Falls back to plain launches.
-    TrainCache& graph = tc;
-    bool& graph_tried = tc.graph_tried;
-    HIPCHK(kh::conv_f32_raw_prepare());          // function attributes are not stream work: set them before any capture
-    static const bool trace = getenv("KAMI_TRAIN_TRACE") != nullptr;
-    const auto t_setup = std::chrono::steady_clock::now();
+    call.t_setup = std::chrono::steady_clock::now();
     for (int epoch = 0; epoch < cfg->epochs; ++epoch) {
         std::shuffle(picker.begin(), picker.end(), rng);
         float avgloss = 0.0f;
@@ -698,33 +725,11 @@ int kh_train(kh_engine* e, const float* inputs, const float* obs_p, const float*
             HIPCHK(hipMemcpyAsync(dx.p, next_input, n_in * 4, hipMemcpyHostToDevice, st));
             HIPCHK(hipMemcpyAsync(dp.p, next_policy, n_p * 4, hipMemcpyHostToDevice, st));
             HIPCHK(hipMemcpyAsync(dv.p, next_value, (size_t)B * 4, hipMemcpyHostToDevice, st));
-            static const bool no_graph = getenv("KAMI_TRAIN_NOGRAPH") != nullptr;
-            if (!graph_tried && no_graph) graph_tried = true;
-            if (!graph_tried) {
-                graph_tried = true;
-                if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                    const hipError_t ce = kh::train_step(*net, sb, dx.as<float>(), dp.as<float>(), dv.as<float>(), B, cfg->lr, dloss.as<float>(), st);
-                    const hipError_t ee = hipStreamEndCapture(st, &graph.g);
-                    if (ce != hipSuccess || ee != hipSuccess || hipGraphInstantiate(&graph.x, graph.g, nullptr, nullptr, 0) != hipSuccess) {
-                        if (graph.x) { (void)hipGraphExecDestroy(graph.x); graph.x = nullptr; }
-                        (void)hipGetLastError();
-                    }
-                    if (trace) fprintf(stderr, "[kami train] step recorded as a graph: %s\n", graph.x ? "yes" : "NO (plain launches)");
-                }
-            }
-            if (graph.x) HIPCHK(hipGraphLaunch(graph.x, st));
-            else HIPCHK(kh::train_step(*net, sb, dx.as<float>(), dp.as<float>(), dv.as<float>(), B, cfg->lr, dloss.as<float>(), st));
+            if ((rc = train_launch_step(call, cfg->lr))) return rc;
             HIPCHK(hipMemcpyAsync(loss_rows, dloss.p, (size_t)B * 2 * 4 + 8, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
-            if (cfg->detect_anomaly) {                        // nn.cpp:337-341: the value output first, then the policy
-                const int* nf = reinterpret_cast<const int*>(loss_rows + 2 * B);
-                if (nf[1]) return fail(KH_ERR_NAN_VALUE, "forward value output contains NaN");
-                if (nf[0]) return fail(KH_ERR_NAN_POLICY, "forward policy output contains NaN");
-            }
-            float lp = 0.0f, lv = 0.0f;
-            for (int b = 0; b < B; ++b) { lp += loss_rows[b]; lv += loss_rows[B + b]; }
-            const float loss = lp + lv / (float)(B * KH_VALUE_WIDTH);
-            if (loss != loss) return fail(KH_ERR_NAN_POLICY, "training loss is NaN (epoch %d, batch %d)", epoch, nbatches);
+            float loss;
+            if ((rc = train_step_result(loss_rows, B, cfg->detect_anomaly != 0, epoch, nbatches, &loss))) return rc;
             avgloss += loss;
             ++nbatches;
         }
@@ -732,25 +737,11 @@ int kh_train(kh_engine* e, const float* inputs, const float* obs_p, const float*
         if (!epoch) firstloss = avgloss;
         lastloss = avgloss;
     }
-    const auto t_steps = std::chrono::steady_clock::now();
-    std::vector<float> blob(nfl);
-    HIPCHK(hipMemcpy(blob.data(), params.p, nfl * 4, hipMemcpyDeviceToHost));
+    call.t_steps = std::chrono::steady_clock::now();
+    if ((rc = train_finish(e, call, trajectories, cfg->epochs))) return rc;
     if (first_loss) *first_loss = firstloss;
     if (last_loss) *last_loss = lastloss;
-    const auto t_read = std::chrono::steady_clock::now();
-    std::shared_ptr<Weights> installed;
-    // every training-mode forward (one per batch, the short last one included: nn.cpp:264-301) counts once in each
-    // BatchNorm's num_batches_tracked
-    const int64_t forwards = (int64_t)cfg->epochs * ((trajectories + B - 1) / B);
-    const int lrc = load_weights_impl(e, blob.data(), nfl, W->generation + 1, W->bn_batches + forwards, &installed);  // nn.cpp:371 ++generation
-    if (lrc == KH_OK) tc.on_device = installed;
-    if (trace) {
-        auto ms = [](std::chrono::steady_clock::duration d) { return std::chrono::duration<double, std::milli>(d).count(); };
-        fprintf(stderr, "[kami train] call: set-up %.2f ms (buffers %.2f, parameters up %.2f, staging %.2f), steps %.2f ms, parameters back %.2f ms, "
-                "weights installed %.2f ms\n", ms(t_setup - t_call), ms(t_bufs - t_call), ms(t_up - t_bufs), ms(t_setup - t_up),
-                ms(t_steps - t_setup), ms(t_read - t_steps), ms(std::chrono::steady_clock::now() - t_read));
-    }
-    return lrc;
+    return KH_OK;
 }
 
 int kh_train_order(int trajectories, int epochs, int32_t* order)

@@ -6,14 +6,17 @@ generation (kami/selfplay.cpp:58-304 without the gating match of evaluate.cpp).
     train     NN.train (kh_train)           the reference's SGD loop on the device        (row f4)
     publish   dist.broadcast_weights        every rank's evaluator gets the new generation (row f3)
 
-Multi-GPU: every rank plays its own shard of the trees with its own engine, rank 0 trains."""
+Multi-GPU: every rank plays its own shard of the trees with its own engine, rank 0 trains.
+
+With a CompactReplay ring the records stay compact all the way: the gathered payloads go into the ring as bytes and rank 0
+trains with NN.train_records (kh_train_records), which expands each batch on the device."""
 from __future__ import annotations
 
 import numpy as np
 
 from . import _lib as L
 from . import dist as kd
-from .replay import ReplayBuffer
+from .replay import CompactReplay, ReplayBuffer
 
 OBSIZE, PSIZE = 8 * 8 * 30, 4672
 
@@ -31,7 +34,7 @@ def records_to_arrays(nn, records):
     return planes, mcts, vals
 
 
-def generation(nn, pool, replay: ReplayBuffer, *, play_evals: int, play_seconds: float = 60.0, sample: int | None = None,
+def generation(nn, pool, replay: "ReplayBuffer | CompactReplay", *, play_evals: int, play_seconds: float = 60.0, sample: int | None = None,
                mlr: int = 5, epochs: int = 8, batchsize: int = 8, dist=None, device: str | None = None):
     """Play, collect, train (rank 0), publish.  Returns a dict of what happened.  The collectives' tensors live where
     the group's backend needs them (kd.collective_device: device memory for RCCL, host memory for gloo)."""
@@ -40,12 +43,22 @@ def generation(nn, pool, replay: ReplayBuffer, *, play_evals: int, play_seconds:
     from . import search as S
     from .replay import gather_compact
     st = pool.run(min_evals=play_evals, max_seconds=play_seconds)
-    mine = pool.drain()
-    # merge over the ranks as COMPACT records (664 B each); the root expands them (device encoder) into its ring
-    payload = b"".join(bytes(r) for r in mine)
+    compact = isinstance(replay, CompactReplay)
+    # merge over the ranks as COMPACT records (664 B each); into a dense ring the root expands them (device encoder)
+    if compact:
+        payload = pool.drain_bytes()
+        mine = range(len(payload) // C.sizeof(S.Record))
+    else:
+        mine = pool.drain()
+        payload = b"".join(bytes(r) for r in mine)
     merged = 0
     rank0 = dist is None or dist.get_rank() == 0
     for r, blob in enumerate(gather_compact(dist, payload, C.sizeof(S.Record), root=0, device=device)):
+        if compact:
+            added = replay.add_bytes(blob)
+            if dist is not None and r != dist.get_rank():
+                merged += added
+            continue
         recs = (S.Record * (len(blob) // C.sizeof(S.Record))).from_buffer_copy(blob)
         planes, mcts, vals = records_to_arrays(nn, recs)
         for i in range(len(vals)):
@@ -59,7 +72,11 @@ def generation(nn, pool, replay: ReplayBuffer, *, play_evals: int, play_seconds:
     out = {"evals": st.evals, "games_finished": st.games_finished, "records": len(vals), "merged": merged,
            "generation_before": nn.get_generation()}
     have = min(replay.count(), replay.size())
-    if rank == 0 and have >= batchsize:
+    if rank == 0 and have >= batchsize and compact:
+        n = sample or (have // batchsize) * batchsize
+        first, last = nn.train_records(replay.select(n), mlr=mlr, epochs=epochs, batchsize=batchsize)
+        out.update(first_loss=first, last_loss=last, trained_on=n)
+    elif rank == 0 and have >= batchsize:
         n = sample or (have // batchsize) * batchsize
         src = replay._rng.integers(0, have, n)                               # replaybuffer.h:61-84, over the written slots
         first, last = nn.train(replay.input_buffer[src].reshape(n, 8, 8, 30), replay.mcts_buffer[src], replay.result_buffer[src],

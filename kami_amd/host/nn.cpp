@@ -179,26 +179,47 @@ void NN::infer(float* input, int batch, float* policy, float* value)
     if (rc) raise(rc);
 }
 
-void NN::train(int trajectories, float* inputs, float* obs_p, float* obs_v, bool detect_anomaly)
+// nn.cpp:236-238: the three option keys the reference reads
+static kh_train_config train_options(bool detect_anomaly)
 {
-    // nn.cpp:236-238: the three option keys the reference reads
     kh_train_config cfg;
     std::memset(&cfg, 0, sizeof cfg);
     cfg.lr = (float)options::getInt("training_mlr", 5) / 1000.0f;
     cfg.epochs = options::getInt("training_epochs", 8);
     cfg.batch = options::getInt("training_batchsize", 8);
     cfg.detect_anomaly = detect_anomaly ? 1 : 0;                 // nn.cpp:231-232,329-344: the same three messages
-    float first = 0.0f, last = 0.0f;
-    int rc = kh_train(eng, inputs, obs_p, obs_v, trajectories, &cfg, &first, &last);
-    if (rc) raise(rc);
+    return cfg;
+}
+
+void NN::trained(int epochs, float first, float last)
+{
     std::vector<float> blob(kh_weight_count(features, filters, residuals));
-    if ((rc = kh_get_weights(eng, blob.data(), blob.size()))) raise(rc);
+    if (int rc = kh_get_weights(eng, blob.data(), blob.size())) raise(rc);
     {
         std::lock_guard<std::mutex> lk(g_store_mu);
         g_store[this] = blob;
     }
     std::cout << "Generated model " << get_generation() << ", average loss " << first << " to " << last << " over "
-              << cfg.epochs << " epochs\n";                      // nn.cpp:372
+              << epochs << " epochs\n";                          // nn.cpp:372
+}
+
+void NN::train(int trajectories, float* inputs, float* obs_p, float* obs_v, bool detect_anomaly)
+{
+    const kh_train_config cfg = train_options(detect_anomaly);
+    float first = 0.0f, last = 0.0f;
+    int rc = kh_train(eng, inputs, obs_p, obs_v, trajectories, &cfg, &first, &last);
+    if (rc) raise(rc);
+    trained(cfg.epochs, first, last);
+}
+
+// NN::train on compact records (kh_train_records): the same option keys, the same result bit for bit, the same loss line
+void NN::train_records(int n, const kh_record* records, bool detect_anomaly)
+{
+    const kh_train_config cfg = train_options(detect_anomaly);
+    float first = 0.0f, last = 0.0f;
+    int rc = kh_train_records(eng, records, n, &cfg, &first, &last);
+    if (rc) raise(rc);
+    trained(cfg.epochs, first, last);
 }
 
 // nn.cpp:189-202.  Option "model_format": "torch" writes the reference's own libtorch archive (kh_write_checkpoint),

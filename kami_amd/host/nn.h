@@ -20,6 +20,7 @@
 #include <string>
 
 struct kh_engine;
+struct kh_record;       // include/kami_hip.h: one compact replay record
 
 // kami.cpp:31-32 names two libtorch calls; they only tune libtorch's own CPU thread pools, which
 // do not exist here.  This is an API-surface stub for those two names, not a runtime shim.
@@ -45,6 +46,7 @@ class NN {
 
         void create(int dtype);
         void load_blob(const float* blob, size_t n, int generation);
+        void trained(int epochs, float first, float last);     // after a training call: keep the blob, print nn.cpp:372's line
 
     public:
         NN(int width, int height, int features, int psize, bool force_cpu=false);
@@ -69,6 +71,7 @@ class NN {
         NN* clone();
 
         // engine extras (not in the reference): compact ingest, raw handle, one evaluator per GPU
+        void train_records(int n, const kh_record* records, bool detect_anomaly=false);   // train() from compact replay records
         kh_engine* handle() { return eng; }
         NN(NN* other, int device_index);    // a replica of `other` on another GPU of the node (same weights, same generation)
         void sync_from(NN* other);          // install other's current weights and generation (the weight publish after training)

@@ -3,6 +3,7 @@
 // kh_encode_infer_legal.
 #include "kami_search.h"
 #include "mcts.h"
+#include "replaybuffer.h"
 
 #include <algorithm>
 #include <atomic>
@@ -49,6 +50,31 @@ uint64_t splitmix(uint64_t x)
 extern "C" {
 
 const char* ks_last_error(void) { return g_err.c_str(); }
+
+/* ---- compact replay ring ---- */
+struct ks_ring { CompactReplayBuffer buf; ks_ring(int cap, uint64_t seed) : buf(cap, seed) {} };
+
+ks_ring* ks_ring_new(int capacity, uint64_t seed)
+{
+    if (capacity < 1) { fail("ring capacity must be at least 1"); return nullptr; }
+    return new ks_ring(capacity, seed);
+}
+void ks_ring_free(ks_ring* r) { delete r; }
+int ks_ring_add(ks_ring* r, const ks_record* records, int64_t n)
+{
+    if (!r || n < 0 || (n > 0 && !records)) return fail("ks_ring_add: a ring, a buffer and n >= 0 required");
+    r->buf.add(records, (long)n);
+    return 0;
+}
+int64_t ks_ring_count(ks_ring* r) { return r ? (int64_t)r->buf.count() : 0; }
+int ks_ring_size(ks_ring* r) { return r ? r->buf.size() : 0; }
+void ks_ring_clear(ks_ring* r) { if (r) r->buf.clear(); }
+int ks_ring_select(ks_ring* r, int n, ks_record* out_records)
+{
+    if (!r || n < 0 || (n > 0 && !out_records)) return fail("ks_ring_select: a ring, a buffer and n >= 0 required");
+    r->buf.select_batch(out_records, n);
+    return 0;
+}
 
 int ks_perft(const char* fen, int depth, uint64_t* nodes)
 {
@@ -194,20 +220,8 @@ void finish_game(ks_pool* p, ks_pool::Game& g, float value)
     std::vector<ks_record> out;
     out.reserve(g.trajectory.size());
     for (auto& t : g.trajectory) {
-        ks_record r;
-        memset(&r, 0, sizeof(r));
-        r.board = t.board;
-        r.value = value == 0.0f ? draw_value : t.pov * value;                       // selfplay.cpp:176-184
-        // keep the most visited KS_MAX_RECORD_ACTIONS moves (positions with more legal moves are rare)
-        std::vector<int> idx(t.actions.size());
-        for (size_t i = 0; i < idx.size(); ++i) idx[i] = (int)i;
-        if (idx.size() > KS_MAX_RECORD_ACTIONS) {
-            std::partial_sort(idx.begin(), idx.begin() + KS_MAX_RECORD_ACTIONS, idx.end(), [&](int a, int b) { return t.visits[a] > t.visits[b]; });
-            idx.resize(KS_MAX_RECORD_ACTIONS);
-            std::sort(idx.begin(), idx.end());
-        }
-        r.nact = (int32_t)idx.size();
-        for (size_t i = 0; i < idx.size(); ++i) { r.actions[i] = (int16_t)t.actions[idx[i]]; r.visits[i] = t.visits[idx[i]]; }
+        // selfplay.cpp:176-184; of more than KS_MAX_RECORD_ACTIONS moves the most visited are kept (make_record)
+        const ks_record r = make_record(t.board, value == 0.0f ? draw_value : t.pov * value, t.actions.data(), t.visits.data(), t.actions.size());
         out.push_back(r);
     }
     {

@@ -1,7 +1,9 @@
 // selfplay.cpp — kami::Selfplay on this repository's stack.  Behaviour and option keys follow
 // kami/selfplay.cpp (cited per block); what differs is what SURVEY §8f asks for: trees on the heap,
 // the observation is an 80-byte record, the network returns the legal moves' priors, a finished
-// game's planes are produced by the device encoder in one batch.
+// game's planes are produced by the device encoder in one batch.  Option "replay_compact" = 1 keeps the replay ring
+// in compact records (kh_record, 664 bytes instead of 26 372) and trains from them (NN::train_records): no encode call
+// per finished game, no dense planes or visit vectors on the host.
 #include "selfplay.h"
 #include "env.h"
 #include "evaluate.h"
@@ -24,7 +26,12 @@ namespace {
 
 // one self-play game of an inference thread
 struct Game {
-    struct Step { kh_board board; std::vector<float> visits; float pov; };
+    struct Step {
+        kh_board board;
+        std::vector<float> visits;       // dense [PSIZE]; with replay_compact the shares of `actions` only
+        std::vector<int> actions;        // replay_compact: the root's moves
+        float pov;
+    };
     std::unique_ptr<MCTS> tree;
     std::vector<Step> trajectory;
     std::vector<std::string> moves;      // coordinate notation, for the pgn command
@@ -95,7 +102,12 @@ struct Selfplay::Impl {
     // candidate is published to every replica (selfplay.cpp:282-283).
     std::vector<std::unique_ptr<NN>> replicas;
     std::vector<NN*> engines;
+    // "replay_compact" (default 0: everything as in the reference).  With 1 the ring holds compact records and the
+    // trainer takes them as they are; the one difference from the dense ring is the record's cap of 96 moves (of a
+    // position with more, the 96 most visited are kept), which is why it is opt-in.  The dense ring then has one slot.
+    const bool compact;
     ReplayBuffer replay;
+    CompactReplayBuffer creplay;
     int ibatch, nodes;
     std::vector<std::thread> inference, training;
     std::atomic<bool> wants_pgn{ false };
@@ -103,7 +115,9 @@ struct Selfplay::Impl {
     std::list<std::atomic<int>> partial_trajectories;
 
     Impl(Selfplay* s, NN* m)             // selfplay.cpp:13-19
-        : self(s), model(m), replay(OBSIZE, PSIZE, options::getInt("replaybuffer_size", 512)),
+        : self(s), model(m), compact(options::getInt("replay_compact", 0) != 0),
+          replay(OBSIZE, PSIZE, compact ? 1 : options::getInt("replaybuffer_size", 512)),
+          creplay(compact ? options::getInt("replaybuffer_size", 512) : 1, (uint64_t)time(nullptr)),
           ibatch(options::getInt("selfplay_batch", 16)), nodes(options::getInt("selfplay_nodes", 512))
     {
         engines.push_back(model);
@@ -121,6 +135,14 @@ struct Selfplay::Impl {
     {
         Env& env = g.tree->get_env();
         if (wants_pgn.exchange(false)) ret_pgn = movetext(g, env, value);
+        if (compact) {                   // selfplay.cpp:176-184 on records: nothing is encoded here
+            std::vector<kh_record> recs;
+            recs.reserve(g.trajectory.size());
+            for (const Game::Step& st : g.trajectory)
+                recs.push_back(make_record(st.board, value == 0.0f ? po.draw_value : st.pov * value, st.actions.data(), st.visits.data(), st.actions.size()));
+            creplay.add(recs.data(), (long)recs.size());
+            return;
+        }
         // the game's observations: one device encode for the whole trajectory, then selfplay.cpp:176-184
         const int n = (int)g.trajectory.size();
         std::vector<kh_board> boards((size_t)n);
@@ -169,8 +191,11 @@ struct Selfplay::Impl {
                         Env& env = tree.get_env();
                         Game::Step st;
                         env.record(&st.board);
-                        st.visits.resize(PSIZE);
-                        tree.snapshot(st.visits.data());
+                        if (compact) tree.snapshot_sparse(st.actions, st.visits);
+                        else {
+                            st.visits.resize(PSIZE);
+                            tree.snapshot(st.visits.data());
+                        }
                         st.pov = -env.turn();
                         g.trajectory.push_back(std::move(st));
                         ++open_steps;
@@ -202,10 +227,14 @@ struct Selfplay::Impl {
         std::cout << "Terminating inference thread: " << id << std::endl;
     }
 
+    long ring_count() { return compact ? creplay.count() : replay.count(); }
+    long ring_size() { return compact ? creplay.size() : replay.size(); }
+    void ring_clear() { if (compact) creplay.clear(); else replay.clear(); }
+
     void report_progress(long from, long target)
     {
-        std::cout << "Gen " << model->get_generation() << " RPB " << 100 * (replay.count() - from) / (target - from) << "% ["
-                  << replay.count() - from << " / " << target - from << "] | Partials: ";
+        std::cout << "Gen " << model->get_generation() << " RPB " << 100 * (ring_count() - from) / (target - from) << "% ["
+                  << ring_count() - from << " / " << target - from << "] | Partials: ";
         int inf = 0;
         for (auto& ct : partial_trajectories) std::cout << " Inf " << inf++ << ": " << ct;
         std::cout << std::endl;
@@ -215,14 +244,17 @@ struct Selfplay::Impl {
     {
         std::cout << "TRAIN " << id << ": starting thread " << id << std::endl;
         const std::string modelpath = options::getStr("model_path", "/tmp/model.pt");
-        const long ring = replay.size();
+        const long ring = ring_size();
         const long step = ring * options::getInt("rpb_train_pct", 40) / 100;              // experiences between attempts
         const int samples = (int)(ring * options::getInt("training_sample_pct", 60) / 100);
         const bool detect_anomaly = options::getInt("training_detect_anomaly", 0);
-        std::vector<float> inputs((size_t)samples * OBSIZE), mcts((size_t)samples * PSIZE), results((size_t)samples);
+        std::vector<float> inputs, mcts, results;
+        std::vector<kh_record> records;
+        if (compact) records.resize((size_t)samples);
+        else { inputs.resize((size_t)samples * OBSIZE); mcts.resize((size_t)samples * PSIZE); results.resize((size_t)samples); }
         long target = ring, from = 0;
         while (running()) {
-            if (replay.count() < target) {
+            if (ring_count() < target) {
                 if (id == 0) report_progress(from, target);
                 std::this_thread::sleep_for(std::chrono::milliseconds(1000));
                 continue;
@@ -230,15 +262,20 @@ struct Selfplay::Impl {
             std::cout << "TRAIN " << id << ": training generation " << model->get_generation() << " with " << samples
                       << " trajectories sampled from last " << ring << std::endl;
             NN candidate(model);                                                           // selfplay.cpp:259
-            replay.select_batch(inputs.data(), mcts.data(), results.data(), samples);
-            candidate.train(samples, inputs.data(), mcts.data(), results.data(), detect_anomaly);
+            if (compact) {
+                creplay.select_batch(records.data(), samples);
+                candidate.train_records(samples, records.data(), detect_anomaly);
+            } else {
+                replay.select_batch(inputs.data(), mcts.data(), results.data(), samples);
+                candidate.train(samples, inputs.data(), mcts.data(), results.data(), detect_anomaly);
+            }
             bool accepted = false;
             try {
                 accepted = eval(model, &candidate, id);
             } catch (std::exception& e) {
                 std::cerr << "TRAIN " << id << ": evaluation failed: " << e.what() << std::endl;
             }
-            from = replay.count();
+            from = ring_count();
             if (!accepted) {
                 std::cout << "TRAIN " << id << ": candidate rejected: generation remains " << model->get_generation() << std::endl;
                 target += step;
@@ -248,9 +285,9 @@ struct Selfplay::Impl {
             model->read(modelpath);
             for (auto& r : replicas) r->sync_from(model);                                  // every evaluator serves the new generation
             std::cout << "TRAIN " << id << ": candidate accepted: using new generation " << model->get_generation() << std::endl;
-            if (options::getInt("flush_old_rpb", 1)) replay.clear();
-            from = replay.count();
-            target = std::max(ring, replay.count() + step);
+            if (options::getInt("flush_old_rpb", 1)) ring_clear();
+            from = ring_count();
+            target = std::max(ring, ring_count() + step);
         }
         std::cout << "TRAIN " << id << ": stopping thread" << std::endl;
     }

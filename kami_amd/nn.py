@@ -69,6 +69,35 @@ def write_checkpoint(path: str, blob: np.ndarray, features: int, filters: int, r
     _chk(lib.kh_checkpoint_write(path.encode(), features, filters, residuals, generation, bn_batches, _ptr(b), b.size))
 
 
+def as_records(records) -> np.ndarray:
+    """Records in any of the forms the record calls take -> a contiguous array of _lib.RECORD_DTYPE: a ctypes `Record`
+    array (or a list of `Record`s), a `bytes` payload of whole records, or a NumPy structured / uint8 array of them."""
+    if isinstance(records, np.ndarray):
+        if records.dtype == L.RECORD_DTYPE:
+            return np.ascontiguousarray(records).reshape(-1)
+        raw = np.ascontiguousarray(records).view(np.uint8).reshape(-1)
+    elif isinstance(records, (list, tuple)):
+        raw = np.frombuffer(b"".join(bytes(r) for r in records), np.uint8)
+    else:
+        raw = np.frombuffer(records, np.uint8)         # bytes, bytearray, a ctypes array: anything with a buffer
+    if raw.size % L.RECORD_DTYPE.itemsize:
+        raise ValueError(f"{raw.size} bytes are not a whole number of {L.RECORD_DTYPE.itemsize}-byte records")
+    return raw.view(L.RECORD_DTYPE)
+
+
+def validate_records(records) -> int:
+    """kh_records_validate: the number of records if every one is usable as a training sample (0 <= nact <= 96, actions
+    in [0, 4672) and pairwise distinct); otherwise KamiError with `.bad_index` = the first offending record.  No GPU."""
+    rec = as_records(records)
+    bad = C.c_int(-1)
+    rc = L.load().kh_records_validate(_ptr(rec), rec.size, C.byref(bad))
+    if rc != L.KH_OK:
+        err = KamiError(rc, L.last_error())
+        err.bad_index = bad.value
+        raise err
+    return rec.size
+
+
 class Ticket:
     """An outstanding kh_submit_*: keeps the caller-side buffers alive until wait() (the engine reads and writes them)."""
 
@@ -146,6 +175,26 @@ class NN:
                                 v.ctypes.data_as(C.c_void_p), n, C.byref(cfg), C.byref(first), C.byref(last)))
         self._blob = self.get_weights()
         return first.value, last.value
+
+    def train_records(self, records, *, mlr: int = 5, epochs: int = 8, batchsize: int = 8, detect_anomaly: bool = False):
+        """kh_train_records: train() on compact records (as_records: ctypes, bytes or NumPy), expanded per batch on the
+        device — the same result as train(*expand_records(records)), bit for bit, without the dense arrays."""
+        rec = as_records(records)
+        cfg = L.TrainConfig(mlr / 1000.0, epochs, batchsize, 1 if detect_anomaly else 0)
+        first, last = C.c_float(), C.c_float()
+        _chk(self._lib.kh_train_records(self._h, _ptr(rec), rec.size, C.byref(cfg), C.byref(first), C.byref(last)))
+        self._blob = self.get_weights()
+        return first.value, last.value
+
+    def expand_records(self, records):
+        """kh_expand_records: -> (planes [n,8,8,30], obs_p [n,4672], obs_v [n]), the dense arrays train() takes."""
+        rec = as_records(records)
+        n = rec.size
+        planes = np.empty((n, 8, 8, NFEATURES), np.float32)
+        obs_p = np.empty((n, PSIZE), np.float32)
+        obs_v = np.empty((n,), np.float32)
+        _chk(self._lib.kh_expand_records(self._h, _ptr(rec), n, _ptr(planes), _ptr(obs_p), _ptr(obs_v)))
+        return planes, obs_p, obs_v
 
     def get_weights(self) -> np.ndarray:
         """The engine's current fp32 parameters in blob order (kh_get_weights)."""

@@ -96,6 +96,59 @@ class ReplayBuffer:
         return inserted
 
 
+class CompactReplay:
+    """The same ring over compact records (kh_record, 664 bytes instead of 26 372): libkamisearch.so's ks_ring_*,
+    the one implementation the C++ host uses too.  `select(n)` returns `n` uniform draws with replacement over the whole
+    ring (a never-written slot is the all-zero record, a valid sample) as a NumPy record array — what
+    NN.train_records takes.  `seed` makes the draws repeatable."""
+
+    def __init__(self, bufsize: int, seed: int = 0):
+        from . import search as S
+        from . import _lib as L
+        self._S, self._dtype = S, L.RECORD_DTYPE
+        self.lib = S.load()
+        self.h = self.lib.ks_ring_new(int(bufsize), int(seed) & (2 ** 64 - 1))
+        if not self.h:
+            raise ValueError(self.lib.ks_last_error().decode())
+
+    def add(self, records) -> int:
+        """Records in any form NN.train_records takes; returns how many went in."""
+        from .nn import as_records
+        rec = as_records(records)
+        if self.lib.ks_ring_add(self.h, rec.ctypes.data, rec.size):
+            raise ValueError(self.lib.ks_last_error().decode())
+        return rec.size
+
+    def add_bytes(self, payload: bytes) -> int:
+        """A payload of whole records, as gather_compact returns them per rank."""
+        if len(payload) % self._dtype.itemsize:
+            raise ValueError(f"{len(payload)} bytes are not a whole number of {self._dtype.itemsize}-byte records")
+        return self.add(payload) if payload else 0
+
+    def size(self) -> int:
+        return self.lib.ks_ring_size(self.h)
+
+    def count(self) -> int:
+        return self.lib.ks_ring_count(self.h)
+
+    def clear(self) -> None:
+        self.lib.ks_ring_clear(self.h)
+
+    def select(self, n: int) -> np.ndarray:
+        out = np.zeros(int(n), self._dtype)
+        if self.lib.ks_ring_select(self.h, int(n), out.ctypes.data):
+            raise ValueError(self.lib.ks_last_error().decode())
+        return out
+
+    def close(self) -> None:
+        if getattr(self, "h", None):
+            self.lib.ks_ring_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+
 def gather_compact(dist, payload: bytes, record_bytes: int, root: int = 0, device: str | None = None):
     """Merge fixed-size compact records (ks_record, 664 bytes: board + sparse visit distribution + value —
     include/kami_search.h) over the ranks: 40x less traffic than the dense 26 372-byte rows `gather` moves.

@@ -8,16 +8,9 @@ from . import _lib as L
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libkamisearch.so")
-MAX_RECORD_ACTIONS = 96
-
-
-class Board(C.Structure):
-    """kh_board (include/kami_hip.h); same bytes as kami_amd._lib.BOARD_DTYPE."""
-    _fields_ = [("piece_occ", C.c_uint64 * 6), ("color_occ", C.c_uint64 * 2), ("ply", C.c_int32), ("halfmove_clock", C.c_int32),
-                ("ctm", C.c_uint8), ("castle_rights", C.c_uint8), ("pad", C.c_uint8 * 6)]
-
-
-assert C.sizeof(Board) == 80
+MAX_RECORD_ACTIONS = L.MAX_RECORD_ACTIONS
+Board = L.Board             # kh_board and kh_record live next to the engine's ABI (the trainer takes records too)
+Record = L.Record
 
 
 class PoolConfig(C.Structure):
@@ -33,11 +26,6 @@ class PoolStats(C.Structure):
                 ("white_wins", C.c_int64), ("black_wins", C.c_int64), ("draws", C.c_int64), ("records", C.c_int64),
                 ("seconds", C.c_double), ("evals_per_s", C.c_double), ("mean_batch", C.c_double),
                 ("engine_seconds", C.c_double)]
-
-
-class Record(C.Structure):
-    _fields_ = [("board", Board), ("value", C.c_float), ("nact", C.c_int32),
-                ("actions", C.c_int16 * MAX_RECORD_ACTIONS), ("visits", C.c_float * MAX_RECORD_ACTIONS)]
 
 
 SYMBOLS = {
@@ -60,6 +48,13 @@ SYMBOLS = {
     "ks_pool_run": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.POINTER(PoolStats)]),
     "ks_pool_drain_records": (C.c_int64, [C.c_void_p, C.POINTER(Record), C.c_int64]),
     "ks_pool_destroy": (None, [C.c_void_p]),
+    "ks_ring_new": (C.c_void_p, [C.c_int, C.c_uint64]),
+    "ks_ring_free": (None, [C.c_void_p]),
+    "ks_ring_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
+    "ks_ring_count": (C.c_int64, [C.c_void_p]),
+    "ks_ring_size": (C.c_int, [C.c_void_p]),
+    "ks_ring_clear": (None, [C.c_void_p]),
+    "ks_ring_select": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "ks_last_error": (C.c_char_p, []),
 }
 
@@ -206,6 +201,12 @@ class Pool:
         buf = (Record * cap)()
         n = self.lib.ks_pool_drain_records(self.h, buf, cap)
         return buf[:n]
+
+    def drain_bytes(self, cap=1 << 16) -> bytes:
+        """drain() as one payload of whole records (what gather_compact and CompactReplay.add_bytes take)."""
+        buf = (Record * cap)()
+        n = self.lib.ks_pool_drain_records(self.h, buf, cap)
+        return C.string_at(buf, n * C.sizeof(Record))
 
     def close(self):
         if getattr(self, "h", None):
