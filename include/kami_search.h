@@ -4,6 +4,7 @@
  *   kami::Env      kami/env.h:41-485      rules, action code, terminal test   (kami_amd/host/env.h)
  *   kami::MCTS     kami/mcts.h:66-349     PUCT search                         (kami_amd/host/mcts.h)
  *   Selfplay::inference_main  kami/selfplay.cpp:58-213   the batch loop       (ks_pool_*)
+ *   kami::eval     kami/evaluate.cpp:10-160   the gating match                (ks_match_*, kami_amd/host/match.cpp)
  * and hands positions to the engine of kami_hip.h as compact records + legal-action lists
  * (kh_encode_infer_legal), so 80 bytes go in and one prior per legal move comes back per leaf.
  * The ks_env_* / ks_mcts_* entry points exist so that the mirrors can be checked against the
@@ -92,6 +93,70 @@ int  ks_pool_publish_weights(ks_pool* p, const float* blob, size_t nfloats, int 
 int  ks_pool_run(ks_pool* p, int64_t min_evals, double max_seconds, ks_pool_stats* stats);
 int64_t ks_pool_drain_records(ks_pool* p, ks_record* out, int64_t cap);
 void ks_pool_destroy(ks_pool* p);
+
+/* ---- gating match (kami/evaluate.cpp:10-160) ---------------------------------------------------------------- */
+/* The candidate plays `games` games against the current model on host worker threads.  One shared tree per game, expanded
+ * without bootstrap; a tree's leaves are evaluated by the model whose turn it is at that tree's ROOT (evaluate.cpp:68-92);
+ * at `nodes` visits the move is the visit maximum; the game ends at Env::terminal.  Game g's tree is seeded like the
+ * pool's, seed * 2654435761u + g.  Colours are fixed and balanced (the reference draws them with rand()).
+ *
+ * Verdict: the reference's arithmetic replayed in game-index order, game k counted only once games 0..k are all over:
+ *   target = (float)((games * target_pct) / 100)            integer division, evaluate.cpp:109
+ *   score += result_for_candidate / 2 + 0.5;  fail if score + (games - counted) < target;
+ *   pass early if score >= target && counted < games;  after the last game pass iff score * 100 / games >= target_pct
+ * (so with 10 games at 54 % five points before the tenth game pass and five points after it do not, as in the reference).
+ * accepted, score and games_counted do not depend on early_stop.
+ *
+ * Determinism: with engines created with KH_VALUE_PER_SAMPLE0 a game's moves and result depend only on the two parameter
+ * sets and dtypes, seed, g, nodes, leaves_per_tree, cpuct, noise_weight and the game's colour — not on threads, pipeline,
+ * early_stop (for the games that finish) or what else shares a launch.  NOT claimed for KH_VALUE_REFERENCE_FLAT engines
+ * (what kami::NN creates): there the value of a leaf depends on the caller's batch, as in the reference; the match runs
+ * with them all the same.
+ *
+ * The match leaves the engines' coalescing settings alone and may share `current` with a running pool: a refused
+ * kh_submit_* (the engine's KH_MAX_OUTSTANDING tickets are shared) is made as the synchronous call, same bits.  A failed
+ * engine call returns 1 with kh_last_error()'s text in ks_last_error(), no ticket left un-waited. */
+typedef struct ks_match_config {
+    int32_t games;            /* "evaluate_games": exactly this many games, one tree each            */
+    int32_t threads;          /* host workers; game g belongs to worker g * T / games                */
+    int32_t nodes;            /* "evaluate_nodes"                                                     */
+    int32_t leaves_per_tree;  /* positions of one tree in flight per round (1 = reference schedule)   */
+    int32_t target_pct;       /* "evaluate_target_pct"                                                */
+    float   cpuct, noise_weight;
+    uint32_t seed;
+    int32_t candidate_white_first;  /* 1: candidate is white in even games, 0: in odd games           */
+    int32_t pipeline;         /* 0: blocking calls, current then candidate (evaluate.cpp:136-151);
+                                 1: both models' rows submitted, then both waited for;
+                                 2: as 1 with each worker's trees in two sets, one in flight while
+                                    the other is expanded and selected                                */
+    int32_t early_stop;       /* 1: stop as soon as the verdict is decided                            */
+    int32_t reserved[5];
+} ks_match_config;
+
+typedef struct ks_match_game {      /* one row per game, index = game number */
+    int32_t finished;               /* 0: cut off by early_stop / skip                                */
+    int32_t candidate_white;
+    int32_t plies;
+    float   result;                 /* Env::terminal's value, white's point of view: +1 / 0 / -1      */
+    int32_t move_offset;            /* this game's action codes: moves[move_offset .. +plies)         */
+} ks_match_game;
+
+typedef struct ks_match_result {
+    int32_t accepted, skipped;      /* skipped: evaluate.cpp:53-59 (current generation >= candidate), checked every round */
+    int32_t games_counted;          /* games the verdict looked at                                    */
+    float   score;                  /* candidate's points over games_counted                          */
+    int32_t candidate_wins, current_wins, draws;      /* over the finished games                      */
+    int64_t evals_current, evals_candidate, batches, moves;
+    double  seconds;
+} ks_match_result;
+
+/* games: [cfg->games] rows or NULL; moves: room for moves_cap action codes or NULL (too small a room is an error) */
+int ks_match_run(kh_engine* current, kh_engine* candidate, const ks_match_config* cfg, ks_match_result* out,
+                 ks_match_game* games, int32_t* moves, int64_t moves_cap);
+/* The same loop and verdict on the CPU: the two evaluators are ks_mcts_synthetic's hash evaluator with the salt mixed
+ * into the position hash.  pipeline is ignored; nothing is ever skipped. */
+int ks_match_synthetic(uint64_t salt_current, uint64_t salt_candidate, const ks_match_config* cfg, ks_match_result* out,
+                       ks_match_game* games, int32_t* moves, int64_t moves_cap);
 
 /* ---- compact replay ring (kami/replaybuffer.h:10-92 over ks_record) ----------------------------------------- */
 /* A fixed ring of `capacity` records under one mutex.  count = records ever added (it keeps counting past the capacity,

@@ -84,16 +84,18 @@ def build_all(force: bool = False, verbose: bool = False) -> str:
 
 
 SEARCH_LIB = os.path.join(HERE, "libkamisearch.so")
+SEARCH_SOURCES = ["search_api.cpp", "match.cpp"]
 
 
 def build_search(force: bool = False, verbose: bool = False) -> str:
-    """libkamisearch.so: the host side that feeds the engine (rules, MCTS, self-play pool; include/kami_search.h).
-    Plain C++, linked against libkamihip.so for kh_encode_infer_legal."""
+    """libkamisearch.so: the host side that feeds the engine (rules, MCTS, self-play pool, gating match;
+    include/kami_search.h).  Plain C++, linked against libkamihip.so for kh_encode_infer_legal."""
     host = os.path.join(HERE, "host")
-    srcs = [os.path.join(host, f) for f in ("search_api.cpp", "mcts.h", "env.h", "chess.h")]
+    units = [os.path.join(host, f) for f in SEARCH_SOURCES]
+    srcs = units + [os.path.join(host, f) for f in ("search_internal.h", "mcts.h", "env.h", "chess.h", "replaybuffer.h")]
     srcs += [os.path.join(os.path.dirname(HERE), "include", f) for f in ("kami_search.h", "kami_hip.h")]
     if force or _stale(SEARCH_LIB, srcs + [LIB]):
-        cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-I" + os.path.join(os.path.dirname(HERE), "include"), "-o", SEARCH_LIB, srcs[0],
+        cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", "-I" + os.path.join(os.path.dirname(HERE), "include"), "-o", SEARCH_LIB] + units + [
                f"-L{HERE}", "-lkamihip", "-Wl,-rpath,$ORIGIN", "-lpthread"]
         if verbose:
             print(" ".join(cmd), flush=True)

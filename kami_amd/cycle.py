@@ -1,9 +1,10 @@
-"""One generation of kami's outer loop on this stack: self-play -> replay records -> NN::train -> new
-generation (kami/selfplay.cpp:58-304 without the gating match of evaluate.cpp).
+"""One generation of kami's outer loop on this stack: self-play -> replay records -> NN::train -> gating match
+(optional: `gate`) -> new generation (kami/selfplay.cpp:58-304, the match of evaluate.cpp included).
 
     play      kami_amd.search.Pool          MCTS trees -> kh_encode_infer_legal           (rows f1, f2)
     collect   gather_compact + ReplayBuffer finished games' positions, merged over ranks as 664-byte records (row f3)
     train     NN.train (kh_train)           the reference's SGD loop on the device        (row f4)
+    gate      kami_amd.search.Match         candidate against current, installed if accepted (selfplay.cpp:274)
     publish   dist.broadcast_weights        every rank's evaluator gets the new generation (row f3)
 
 Multi-GPU: every rank plays its own shard of the trees with its own engine, rank 0 trains.
@@ -35,9 +36,12 @@ def records_to_arrays(nn, records):
 
 
 def generation(nn, pool, replay: "ReplayBuffer | CompactReplay", *, play_evals: int, play_seconds: float = 60.0, sample: int | None = None,
-               mlr: int = 5, epochs: int = 8, batchsize: int = 8, dist=None, device: str | None = None):
+               mlr: int = 5, epochs: int = 8, batchsize: int = 8, dist=None, device: str | None = None, gate: dict | None = None):
     """Play, collect, train (rank 0), publish.  Returns a dict of what happened.  The collectives' tensors live where
-    the group's backend needs them (kd.collective_device: device memory for RCCL, host memory for gloo)."""
+    the group's backend needs them (kd.collective_device: device memory for RCCL, host memory for gloo).
+    gate=None: the trained weights are installed unconditionally.  gate=dict(...): rank 0 trains a clone of `nn`, plays
+    search.Match(nn, clone, **gate) and installs the clone's weights and generation on `nn` only if it is accepted
+    (selfplay.cpp:259-287); the result gains accepted, gate_score, gate_games."""
     device = device or kd.collective_device(dist)
     import ctypes as C
     from . import search as S
@@ -72,16 +76,25 @@ def generation(nn, pool, replay: "ReplayBuffer | CompactReplay", *, play_evals: 
     out = {"evals": st.evals, "games_finished": st.games_finished, "records": len(vals), "merged": merged,
            "generation_before": nn.get_generation()}
     have = min(replay.count(), replay.size())
+    trainee = nn.clone() if gate is not None and rank == 0 and have >= batchsize else nn      # selfplay.cpp:259
     if rank == 0 and have >= batchsize and compact:
         n = sample or (have // batchsize) * batchsize
-        first, last = nn.train_records(replay.select(n), mlr=mlr, epochs=epochs, batchsize=batchsize)
+        first, last = trainee.train_records(replay.select(n), mlr=mlr, epochs=epochs, batchsize=batchsize)
         out.update(first_loss=first, last_loss=last, trained_on=n)
     elif rank == 0 and have >= batchsize:
         n = sample or (have // batchsize) * batchsize
         src = replay._rng.integers(0, have, n)                               # replaybuffer.h:61-84, over the written slots
-        first, last = nn.train(replay.input_buffer[src].reshape(n, 8, 8, 30), replay.mcts_buffer[src], replay.result_buffer[src],
+        first, last = trainee.train(replay.input_buffer[src].reshape(n, 8, 8, 30), replay.mcts_buffer[src], replay.result_buffer[src],
                                mlr=mlr, epochs=epochs, batchsize=batchsize)
         out.update(first_loss=first, last_loss=last, trained_on=n)
+    if gate is not None:
+        out.update(accepted=False, gate_score=0.0, gate_games=0)             # (nothing trained, or not the training rank)
+    if trainee is not nn:
+        res = S.Match(nn, trainee, **gate).run()                             # selfplay.cpp:274
+        out.update(accepted=bool(res.accepted), gate_score=res.score, gate_games=res.games_counted)
+        if res.accepted:
+            nn.load_weights(trainee.get_weights(), trainee.get_generation())
+        trainee.close()
     if dist is not None:
         blob, gen = kd.broadcast_weights(dist, nn.get_weights() if rank == 0 else None, nn.get_generation() if rank == 0 else 0,
                                          src=0, device=device, as_tensor=True)      # stays in device memory under RCCL

@@ -4,6 +4,7 @@
 #include "kami_search.h"
 #include "mcts.h"
 #include "replaybuffer.h"
+#include "search_internal.h"
 
 #include <algorithm>
 #include <atomic>
@@ -17,10 +18,13 @@
 #include <thread>
 
 using namespace kami;
+using kami::detail::fail;
 
 namespace {
 thread_local std::string g_err;
-int fail(const char* fmt, ...)
+}  // namespace
+
+int kami::detail::fail(const char* fmt, ...)
 {
     char buf[512];
     va_list ap;
@@ -30,22 +34,6 @@ int fail(const char* fmt, ...)
     g_err = buf;
     return 1;
 }
-
-// the synthetic evaluator of the reference harness (`kami_ref mcts`, test infrastructure)
-uint64_t fnv1a(const std::string& s)
-{
-    uint64_t h = 1469598103934665603ull;
-    for (unsigned char c : s) { h ^= c; h *= 1099511628211ull; }
-    return h;
-}
-uint64_t splitmix(uint64_t x)
-{
-    x += 0x9e3779b97f4a7c15ull;
-    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
-    x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
-}  // namespace
 
 extern "C" {
 
@@ -152,21 +140,9 @@ int ks_mcts_synthetic(int nodes, int nmoves, int leaves, const int32_t* picks, i
                     else if (tree.n() + nb >= nodes) break;         // a terminal visit was counted
                 }
                 for (int j = 0; j < nb; ++j) {
-                    // the evaluator sees the leaf position: rebuild its FEN by replaying the path
-                    std::vector<int> path;
-                    for (size_t d = 1; d < batch[j].path.size(); ++d) path.push_back(batch[j].path[d]->action);
-                    Env& e = tree.get_env();
-                    for (int a : path) e.push(a);
-                    const uint64_t h = fnv1a(e.print());
-                    for (size_t k = 0; k < path.size(); ++k) e.pop();
-                    double sum = 0.0;
-                    for (int a = 0; a < PSIZE; ++a) { policy[a] = (float)(splitmix(h + (uint64_t)a) % 16777213ull + 1); sum += policy[a]; }
-                    for (int a = 0; a < PSIZE; ++a) policy[a] = (float)(policy[a] / sum);
-                    const float value = ((float)(splitmix(h ^ 0x7777) % 2001) - 1000.0f) / 1000.0f;
-                    float ptotal = 0.0f;
-                    for (int a : batch[j].actions) ptotal += policy[a];
+                    float value;
                     std::vector<float> pr(batch[j].actions.size());
-                    for (size_t i = 0; i < pr.size(); ++i) pr[i] = policy[batch[j].actions[i]] / ptotal;
+                    detail::synthetic_eval(detail::leaf_hash(tree, batch[j]), batch[j].actions, policy.data(), pr.data(), &value);
                     tree.expand_leaf(batch[j], pr.data(), value);
                 }
             }

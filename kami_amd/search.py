@@ -28,6 +28,28 @@ class PoolStats(C.Structure):
                 ("engine_seconds", C.c_double)]
 
 
+class MatchConfig(C.Structure):
+    _fields_ = [("games", C.c_int32), ("threads", C.c_int32), ("nodes", C.c_int32), ("leaves_per_tree", C.c_int32),
+                ("target_pct", C.c_int32), ("cpuct", C.c_float), ("noise_weight", C.c_float), ("seed", C.c_uint32),
+                ("candidate_white_first", C.c_int32), ("pipeline", C.c_int32), ("early_stop", C.c_int32),
+                ("reserved", C.c_int32 * 5)]
+
+
+class MatchGame(C.Structure):
+    _fields_ = [("finished", C.c_int32), ("candidate_white", C.c_int32), ("plies", C.c_int32), ("result", C.c_float),
+                ("move_offset", C.c_int32)]
+
+
+class MatchResult(C.Structure):
+    _fields_ = [("accepted", C.c_int32), ("skipped", C.c_int32), ("games_counted", C.c_int32), ("score", C.c_float),
+                ("candidate_wins", C.c_int32), ("current_wins", C.c_int32), ("draws", C.c_int32),
+                ("evals_current", C.c_int64), ("evals_candidate", C.c_int64), ("batches", C.c_int64), ("moves", C.c_int64),
+                ("seconds", C.c_double)]
+    games = ()      # run() / match_synthetic(): one (finished, candidate_white, result, [moves]) per game
+
+
+_MATCH_TAIL = [C.POINTER(MatchConfig), C.POINTER(MatchResult), C.POINTER(MatchGame), C.POINTER(C.c_int32), C.c_int64]
+
 SYMBOLS = {
     "ks_perft": (C.c_int, [C.c_char_p, C.c_int, C.POINTER(C.c_uint64)]),
     "ks_fen_actions": (C.c_int, [C.c_char_p, C.POINTER(C.c_int32), C.c_int]),
@@ -48,6 +70,8 @@ SYMBOLS = {
     "ks_pool_run": (C.c_int, [C.c_void_p, C.c_int64, C.c_double, C.POINTER(PoolStats)]),
     "ks_pool_drain_records": (C.c_int64, [C.c_void_p, C.POINTER(Record), C.c_int64]),
     "ks_pool_destroy": (None, [C.c_void_p]),
+    "ks_match_run": (C.c_int, [C.c_void_p, C.c_void_p] + _MATCH_TAIL),
+    "ks_match_synthetic": (C.c_int, [C.c_uint64, C.c_uint64] + _MATCH_TAIL),
     "ks_ring_new": (C.c_void_p, [C.c_int, C.c_uint64]),
     "ks_ring_free": (None, [C.c_void_p]),
     "ks_ring_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64]),
@@ -148,6 +172,51 @@ def mcts_synthetic(nodes: int, nmoves: int, leaves: int = 1, picks=None) -> str:
     if lib.ks_mcts_synthetic(nodes, nmoves, leaves, arr, len(picks), buf, len(buf)):
         raise RuntimeError(lib.ks_last_error().decode())
     return buf.value.decode()
+
+
+MATCH_MAX_PLIES = 8192     # room per game for the move lists (the 50-ply draw rule ends real games long before)
+
+
+def _match(call, games, threads, nodes, leaves_per_tree, target_pct, cpuct, noise_weight, seed, candidate_white_first,
+           pipeline, early_stop):
+    """The tail ks_match_run and ks_match_synthetic share: config in, result struct with `.games` out."""
+    cfg = MatchConfig(games, threads, nodes, leaves_per_tree, target_pct, cpuct, noise_weight, seed,
+                      int(bool(candidate_white_first)), int(pipeline), int(bool(early_stop)))
+    res = MatchResult()
+    rows = (MatchGame * max(1, games))()
+    cap = max(1, games) * MATCH_MAX_PLIES
+    moves = (C.c_int32 * cap)()
+    if call(C.byref(cfg), C.byref(res), rows, moves, cap):
+        raise RuntimeError(load().ks_last_error().decode())
+    res.games = [(r.finished, r.candidate_white, r.result, list(moves[r.move_offset:r.move_offset + r.plies])) for r in rows[:games]]
+    return res
+
+
+def match_synthetic(salt_current: int, salt_candidate: int, games=10, threads=4, nodes=512, leaves_per_tree=1, target_pct=54,
+                    cpuct=1.0, noise_weight=0.05, seed=1, candidate_white_first=True, pipeline=1, early_stop=True):
+    """ks_match_synthetic: Match's loop and verdict on the CPU, the two evaluators being mcts_synthetic's with a salt each."""
+    lib = load()
+    return _match(lambda *tail: lib.ks_match_synthetic(salt_current, salt_candidate, *tail), games, threads, nodes,
+                  leaves_per_tree, target_pct, cpuct, noise_weight, seed, candidate_white_first, pipeline, early_stop)
+
+
+class Match:
+    """The gating match (kami/evaluate.cpp:10-160) of `candidate` against `current` (two kami_amd.NN) on host workers:
+    ks_match_run.  run() returns the ks_match_result struct with `.games`, one (finished, candidate_white, result, [moves])
+    per game; a failed engine call raises RuntimeError with the engine's message and the object can be run again."""
+
+    def __init__(self, current, candidate, games=10, threads=4, nodes=512, leaves_per_tree=1, target_pct=54, cpuct=1.0,
+                 noise_weight=0.05, seed=1, candidate_white_first=True, pipeline=1, early_stop=True):
+        self.lib = load()
+        self.current, self.candidate = current, candidate          # kept alive for the duration
+        self.args = (games, threads, nodes, leaves_per_tree, target_pct, cpuct, noise_weight, seed, candidate_white_first,
+                     pipeline, early_stop)
+
+    def run(self):
+        cur, cand = self.current.handle, self.candidate.handle
+        if not cur or not cand:
+            raise RuntimeError("the match's engines are closed")
+        return _match(lambda *tail: self.lib.ks_match_run(cur, cand, *tail), *self.args)
 
 
 import weakref
