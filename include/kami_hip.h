@@ -131,8 +131,37 @@ typedef struct kh_train_config {
                                fails with the reference's messages "training input ind <i> contains NaN" (KH_ERR_INVALID),
                                "forward value output contains NaN" (KH_ERR_NAN_VALUE), "forward policy output contains NaN"
                                (KH_ERR_NAN_POLICY); the parameters stay as they were before the call */
-    int32_t reserved[4];
+    /* Optimizer options.  All zero (a zeroed struct, what every earlier caller built) is the reference's plain SGD, bit
+     * for bit.  Otherwise one step restates torch.nn.utils.clip_grad_norm_(params, max_grad_norm) followed by
+     * torch.optim.SGD(lr, momentum, dampening=0, weight_decay, nesterov).step(), in fp32, in this order:
+     *   1. max_grad_norm > 0: norm = sqrt(sum g^2) over all trainable entries, c = min(1, max_grad_norm / (norm + 1e-6)),
+     *      g <- g * c
+     *   2. g <- g + weight_decay * p
+     *   3. v <- momentum * v + g
+     *   4. d = nesterov ? g + momentum * v : v          (momentum == 0: d = g)
+     *   5. p <- p - lr * d
+     * "Trainable" is every blob tensor except the BatchNorm running_mean / running_var slots: those are written only by
+     * the training-mode forward, and weight decay never touches them.  The velocity v is per call, like the reference's
+     * optim::SGD object (nn.cpp:238-240): zero at the start of every kh_train / kh_train_records, never part of the
+     * weights (not cloned, not in checkpoints, not in kh_get_weights).  The norm is summed in a fixed order that depends
+     * only on the blob size: the same call from the same weights gives the same bits on every device. */
+    float   momentum;       /* mu in [0, 1); 0 = off                                  */
+    float   weight_decay;   /* L2 coefficient >= 0 added to the gradient; 0 = off     */
+    float   max_grad_norm;  /* > 0: clip the global L2 norm of the gradient; 0 = off  */
+    int32_t nesterov;       /* 0 / 1; 1 requires momentum > 0                         */
 } kh_train_config;
+/* What kh_train and kh_train_records accept, checked without an engine or a GPU: KH_OK, or KH_ERR_INVALID with a message
+ * that names the field — batch < 2, epochs < 1, a NaN or infinite momentum / weight_decay / max_grad_norm, momentum
+ * outside [0, 1), a negative weight_decay or max_grad_norm, nesterov not 0 / 1, nesterov with momentum == 0.  Both
+ * training calls run it before any device work: a rejected call leaves parameters, generation and kh_bn_batches alone. */
+int  kh_train_config_check(const kh_train_config* cfg);
+/* The gradient norm BEFORE clipping of every step of this engine's last completed training call that ran with
+ * max_grad_norm > 0, in step order: up to `cap` of them into norms (nullable when cap == 0), their number in *steps
+ * (0 if that call did not clip, or none has completed).  To calibrate the threshold, train once with a huge
+ * max_grad_norm (c is then exactly 1) and read the norms.  A step whose norm is not finite fails its training call like
+ * a NaN loss does: "training gradient norm is not finite (epoch %d, batch %d)", checked after the loss, nothing
+ * installed. */
+int  kh_train_grad_norms(kh_engine* e, float* norms, int cap, int* steps);
 int  kh_train(kh_engine* e, const float* inputs, const float* obs_p, const float* obs_v, int trajectories,
               const kh_train_config* cfg, float* first_loss, float* last_loss);
 /* The order kh_train visits the samples in: order[epoch * trajectories + k] = index of the k-th sample of that epoch (one

@@ -53,7 +53,9 @@ assert C.sizeof(Board) == 80 and C.sizeof(Record) == 664 and RECORD_DTYPE.itemsi
 # every symbol include/kami_hip.h declares: name -> (restype, argtypes)
 _P = C.c_void_p
 class TrainConfig(C.Structure):
-    _fields_ = [("lr", C.c_float), ("epochs", C.c_int32), ("batch", C.c_int32), ("detect_anomaly", C.c_int32), ("reserved", C.c_int32 * 4)]
+    """kh_train_config (32 bytes); the optimizer fields default to 0 = the reference's plain SGD."""
+    _fields_ = [("lr", C.c_float), ("epochs", C.c_int32), ("batch", C.c_int32), ("detect_anomaly", C.c_int32),
+                ("momentum", C.c_float), ("weight_decay", C.c_float), ("max_grad_norm", C.c_float), ("nesterov", C.c_int32)]
 
 
 SYMBOLS = {
@@ -63,6 +65,8 @@ SYMBOLS = {
     "kh_load_weights": (C.c_int, [_P, _P, C.c_size_t, C.c_int]),
     "kh_load_weights_device": (C.c_int, [_P, _P, C.c_size_t, C.c_int, _P]),
     "kh_train": (C.c_int, [_P, _P, _P, _P, C.c_int, C.POINTER(TrainConfig), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "kh_train_config_check": (C.c_int, [C.POINTER(TrainConfig)]),
+    "kh_train_grad_norms": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
     "kh_train_order": (C.c_int, [C.c_int, C.c_int, _P]),
     "kh_records_validate": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "kh_expand_records": (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),

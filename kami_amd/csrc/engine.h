@@ -4,6 +4,7 @@
 // is include/kami_hip.h).
 #pragma once
 #include "kh_internal.h"
+#include "train_opt.h"
 
 #include <atomic>
 #include <chrono>
@@ -111,6 +112,9 @@ struct Queue;           // the submit / wait queue (queue.hip)
 // into dx / dp / dv and run the same recorded step on it, so alternating them on one engine re-records nothing.
 struct TrainCache {
     DevMem params, grads, work, dx, dp, dv, dloss;
+    DevMem vel, norm_part, frozen;              // optimizer options only: the velocity (blob-shaped, zeroed per call), the norm's
+                                                // partial sums, the running-statistics slots' ranges (uploaded once: one shape per engine)
+    std::vector<float> last_norms;              // kh_train_grad_norms: the last completed call's norms before clipping
     DevMem rec, order;                          // kh_train_records: the call's records (RecordBlock layout) and sample order
     PinMem pin, pin_params;                     // batch staging; the parameter blob on its way up (a pageable source made the
                                                 // upload take 0.1 ms or 10-27 ms from call to call: the runtime pins it on the fly)
@@ -121,7 +125,7 @@ struct TrainCache {
     hipGraph_t g = nullptr;
     hipGraphExec_t x = nullptr;
     int B = 0;
-    float lr = 0.0f;
+    StepOpt opt{};
     bool valu = false, graph_tried = false;
     void drop_graph()
     {
@@ -240,14 +244,17 @@ struct TrainCall {
     hipStream_t st = nullptr;
     size_t nfl = 0;
     int B = 0;
+    StepOpt opt{};
+    std::vector<float> norms;                                    // max_grad_norm > 0: every step's norm before clipping so far
     std::chrono::steady_clock::time_point t_call, t_bufs, t_up, t_setup, t_steps;   // KAMI_TRAIN_TRACE
 };
 // weights, lock, workspace (drops the recorded step when what it holds changed), stream, parameters on the device
 int train_begin(kh_engine* e, const kh_train_config* cfg, const char* who, TrainCall& c);
 // one SGD step on dx / dp / dv -> dloss: the recorded graph (recorded at the first step) or plain launches
-int train_launch_step(TrainCall& c, float lr);
-// nn.cpp:337-341 and the loss of one step from its dloss block ([2B] rows + the two NaN flags), as kh_train reports them
-int train_step_result(const float* loss_rows, int B, bool detect_anomaly, int epoch, int batch, float* loss);
+int train_launch_step(TrainCall& c);
+// nn.cpp:337-341 and the loss of one step from its dloss block (train_result_floats(B)), as kh_train reports them; with
+// max_grad_norm > 0 the step's gradient norm joins c.norms, and a norm that is not finite fails like a NaN loss
+int train_step_result(TrainCall& c, const float* loss_rows, bool detect_anomaly, int epoch, int batch, float* loss);
 // parameters back, installed as generation + 1 with the BatchNorm counter advanced
 int train_finish(kh_engine* e, TrainCall& c, int trajectories, int epochs);
 

@@ -14,6 +14,7 @@
 #include <sched.h>
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -507,6 +508,7 @@ int train_begin(kh_engine* e, const kh_train_config* cfg, const char* who, Train
     c.net.reset(kh::train_layout_new(F, C, R));
     c.nfl = c.W->blob.size();
     c.B = B;
+    c.opt = kh::StepOpt{ cfg->lr, cfg->momentum, cfg->weight_decay, cfg->max_grad_norm, cfg->nesterov };
     const size_t nfl = c.nfl;
     c.lock = std::unique_lock<std::mutex>(e->train_mu);       // one trainer per engine at a time (the reference: exclusive lock, nn.cpp:226)
     if (!e->train) e->train = new TrainCache();
@@ -515,15 +517,28 @@ int train_begin(kh_engine* e, const kh_train_config* cfg, const char* who, Train
     DevMem &params = tc.params, &grads = tc.grads, &work = tc.work, &dx = tc.dx, &dp = tc.dp, &dv = tc.dv, &dloss = tc.dloss;
     const bool valu_now = getenv("KAMI_TRAIN_VALU") && atoi(getenv("KAMI_TRAIN_VALU")) != 0;
     {
-        const void* before[3] = { params.p, work.p, dx.p };
+        const void* before[6] = { params.p, work.p, dx.p, dloss.p, tc.vel.p, tc.norm_part.p };
         if ((rc = params.ensure(nfl * 4)) || (rc = grads.ensure(nfl * 4)) || (rc = work.ensure(kh::train_workspace_floats(F, C, R, B) * 4)) ||
             (rc = dx.ensure((size_t)B * 64 * F * 4)) || (rc = dp.ensure((size_t)B * KH_PSIZE * 4)) || (rc = dv.ensure((size_t)B * 4)) ||
-            (rc = dloss.ensure((size_t)B * 2 * 4 + 8)))
+            (rc = dloss.ensure(kh::train_result_floats(B) * 4)))
             return rc;
-        // the recorded step holds buffer addresses, the batch size, the learning rate and the kernel choice
-        if (before[0] != params.p || before[1] != work.p || before[2] != dx.p || tc.B != B || tc.lr != cfg->lr || tc.valu != valu_now) tc.drop_graph();
+        if (!c.opt.plain()) {
+            if ((c.opt.momentum != 0.0f && (rc = tc.vel.ensure(nfl * 4))) ||
+                (c.opt.max_grad_norm > 0.0f && (rc = tc.norm_part.ensure(kh::train_norm_parts(nfl) * sizeof(double)))))
+                return rc;
+            if (!tc.frozen.p) {
+                const long long* ranges = nullptr;
+                const size_t nr = kh::train_frozen_ranges(*c.net, &ranges);
+                if ((rc = tc.frozen.ensure(nr * 2 * sizeof(long long)))) return rc;
+                HIPCHK(hipMemcpy(tc.frozen.p, ranges, nr * 2 * sizeof(long long), hipMemcpyHostToDevice));
+            }
+        }
+        // the recorded step holds buffer addresses, the batch size, the update rule's values and the kernel choice
+        if (before[0] != params.p || before[1] != work.p || before[2] != dx.p || before[3] != dloss.p || before[4] != tc.vel.p ||
+            before[5] != tc.norm_part.p || tc.B != B || !(tc.opt == c.opt) || tc.valu != valu_now)
+            tc.drop_graph();
         if (before[0] != params.p) tc.on_device.reset();
-        tc.B = B; tc.lr = cfg->lr; tc.valu = valu_now;
+        tc.B = B; tc.opt = c.opt; tc.valu = valu_now;
     }
     c.t_bufs = std::chrono::steady_clock::now();
     if (!tc.st) HIPCHK(hipStreamCreateWithFlags(&tc.st, hipStreamNonBlocking));
@@ -535,6 +550,7 @@ int train_begin(kh_engine* e, const kh_train_config* cfg, const char* who, Train
         HIPCHK(hipMemcpyAsync(params.p, tc.pin_params.p, nfl * 4, hipMemcpyHostToDevice, c.st));
     }                                            // else: `params` still holds exactly these weights — the previous call trained them
     tc.on_device.reset();                        // (until this call has installed its result, `params` belongs to nobody)
+    if (c.opt.momentum != 0.0f) HIPCHK(hipMemsetAsync(tc.vel.p, 0, nfl * 4, c.st));      // the velocity lives for one call
     c.t_up = std::chrono::steady_clock::now();
     HIPCHK(kh::conv_f32_raw_prepare());          // function attributes are not stream work: set them before any capture
     return KH_OK;
@@ -544,19 +560,25 @@ static const bool train_trace = getenv("KAMI_TRAIN_TRACE") != nullptr;
 
 // A step is ~120 small launches on fixed buffers: recorded once as a graph, replayed per batch (with the
 // tiled conv kernels the host's launch work, not the GPU, bounded a step).  Falls back to plain launches.
-int train_launch_step(TrainCall& c, float lr)
+int train_launch_step(TrainCall& c)
 {
     TrainCache& tc = *c.tc;
     const int B = c.B;
     hipStream_t st = c.st;
     const kh::StepBuffers sb{ tc.params.as<float>(), tc.grads.as<float>(), tc.work.as<float>() };
+    const kh::OptBuffers ob{ tc.vel.as<float>(), tc.norm_part.as<double>(), tc.frozen.as<long long>() };
     float *dx = tc.dx.as<float>(), *dp = tc.dp.as<float>(), *dv = tc.dv.as<float>(), *dloss = tc.dloss.as<float>();
+    // all options zero: the reference's step, the launches every earlier version recorded
+    auto step = [&] {
+        return c.opt.plain() ? kh::train_step(*c.net, sb, dx, dp, dv, B, c.opt.lr, dloss, st)
+                             : kh::train_step_opt(*c.net, sb, ob, dx, dp, dv, B, c.opt, dloss, st);
+    };
     static const bool no_graph = getenv("KAMI_TRAIN_NOGRAPH") != nullptr;
     if (!tc.graph_tried && no_graph) tc.graph_tried = true;
     if (!tc.graph_tried) {
         tc.graph_tried = true;
         if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            const hipError_t ce = kh::train_step(*c.net, sb, dx, dp, dv, B, lr, dloss, st);
+            const hipError_t ce = step();
             const hipError_t ee = hipStreamEndCapture(st, &tc.g);
             if (ce != hipSuccess || ee != hipSuccess || hipGraphInstantiate(&tc.x, tc.g, nullptr, nullptr, 0) != hipSuccess) {
                 if (tc.x) { (void)hipGraphExecDestroy(tc.x); tc.x = nullptr; }
@@ -566,12 +588,13 @@ int train_launch_step(TrainCall& c, float lr)
         }
     }
     if (tc.x) HIPCHK(hipGraphLaunch(tc.x, st));
-    else HIPCHK(kh::train_step(*c.net, sb, dx, dp, dv, B, lr, dloss, st));
+    else HIPCHK(step());
     return KH_OK;
 }
 
-int train_step_result(const float* loss_rows, int B, bool detect_anomaly, int epoch, int batch, float* loss_out)
+int train_step_result(TrainCall& c, const float* loss_rows, bool detect_anomaly, int epoch, int batch, float* loss_out)
 {
+    const int B = c.B;
     if (detect_anomaly) {                                 // nn.cpp:337-341: the value output first, then the policy
         const int* nf = reinterpret_cast<const int*>(loss_rows + 2 * B);
         if (nf[1]) return fail(KH_ERR_NAN_VALUE, "forward value output contains NaN");
@@ -581,6 +604,11 @@ int train_step_result(const float* loss_rows, int B, bool detect_anomaly, int ep
     for (int b = 0; b < B; ++b) { lp += loss_rows[b]; lv += loss_rows[B + b]; }
     const float loss = lp + lv / (float)(B * KH_VALUE_WIDTH);
     if (loss != loss) return fail(KH_ERR_NAN_POLICY, "training loss is NaN (epoch %d, batch %d)", epoch, batch);
+    if (c.opt.max_grad_norm > 0.0f) {
+        const float norm = loss_rows[2 * B + 2];
+        if (!std::isfinite(norm)) return fail(KH_ERR_NAN_POLICY, "training gradient norm is not finite (epoch %d, batch %d)", epoch, batch);
+        c.norms.push_back(norm);
+    }
     *loss_out = loss;
     return KH_OK;
 }
@@ -598,7 +626,7 @@ int train_finish(kh_engine* e, TrainCall& c, int trajectories, int epochs)
     const int64_t forwards = (int64_t)epochs * ((trajectories + c.B - 1) / c.B);
     const int lrc = load_weights_device_impl(e, tc.params.as<float>(), nfl, c.W->generation + 1, c.W->bn_batches + forwards, c.st,
                                              &tc.pin_params, &installed);  // nn.cpp:371 ++generation
-    if (lrc == KH_OK) tc.on_device = installed;
+    if (lrc == KH_OK) { tc.on_device = installed; tc.last_norms = std::move(c.norms); }
     if (train_trace) {
         auto ms = [](std::chrono::steady_clock::duration d) { return std::chrono::duration<double, std::milli>(d).count(); };
         fprintf(stderr, "[kami train] call: set-up %.2f ms (buffers %.2f, parameters up %.2f, staging %.2f), steps %.2f ms, parameters back %.2f ms, "
@@ -690,9 +718,10 @@ int kh_train(kh_engine* e, const float* inputs, const float* obs_p, const float*
 {
     if (!e || !inputs || !obs_p || !obs_v || !cfg) return fail(KH_ERR_INVALID, "null argument");
     if (trajectories < 1 || cfg->batch < 2 || cfg->epochs < 1) return fail(KH_ERR_INVALID, "trajectories >= 1, batch >= 2, epochs >= 1 required");
-    TrainCall call;
-    int rc = train_begin(e, cfg, "kh_train", call);
+    int rc = kh_train_config_check(cfg);
     if (rc) return rc;
+    TrainCall call;
+    if ((rc = train_begin(e, cfg, "kh_train", call))) return rc;
     TrainCache& tc = *call.tc;
     DevMem &dx = tc.dx, &dp = tc.dp, &dv = tc.dv, &dloss = tc.dloss;
     hipStream_t st = call.st;
@@ -706,12 +735,13 @@ int kh_train(kh_engine* e, const float* inputs, const float* obs_p, const float*
     // batch staging in page-locked memory (rows persist from batch to batch like the reference's stack buffers)
     PinMem& pin = tc.pin;
     const size_t n_in = (size_t)B * in_row, n_p = (size_t)B * KH_PSIZE;
-    if (pin.ensure((n_in + n_p + (size_t)B + (size_t)B * 2 + 2) * 4)) return KH_ERR_HIP;
+    const size_t n_res = kh::train_result_floats(B);
+    if (pin.ensure((n_in + n_p + (size_t)B + n_res) * 4)) return KH_ERR_HIP;
     float* next_input = reinterpret_cast<float*>(pin.p);
     float* next_policy = next_input + n_in;
     float* next_value = next_policy + n_p;
     float* loss_rows = next_value + B;
-    memset(pin.p, 0, (n_in + n_p + (size_t)B + (size_t)B * 2 + 2) * 4);
+    memset(pin.p, 0, (n_in + n_p + (size_t)B + n_res) * 4);
     float firstloss = 0.0f, lastloss = 0.0f;
     call.t_setup = std::chrono::steady_clock::now();
     for (int epoch = 0; epoch < cfg->epochs; ++epoch) {
@@ -734,11 +764,11 @@ int kh_train(kh_engine* e, const float* inputs, const float* obs_p, const float*
             HIPCHK(hipMemcpyAsync(dx.p, next_input, n_in * 4, hipMemcpyHostToDevice, st));
             HIPCHK(hipMemcpyAsync(dp.p, next_policy, n_p * 4, hipMemcpyHostToDevice, st));
             HIPCHK(hipMemcpyAsync(dv.p, next_value, (size_t)B * 4, hipMemcpyHostToDevice, st));
-            if ((rc = train_launch_step(call, cfg->lr))) return rc;
-            HIPCHK(hipMemcpyAsync(loss_rows, dloss.p, (size_t)B * 2 * 4 + 8, hipMemcpyDeviceToHost, st));
+            if ((rc = train_launch_step(call))) return rc;
+            HIPCHK(hipMemcpyAsync(loss_rows, dloss.p, n_res * 4, hipMemcpyDeviceToHost, st));
             HIPCHK(hipStreamSynchronize(st));
             float loss;
-            if ((rc = train_step_result(loss_rows, B, cfg->detect_anomaly != 0, epoch, nbatches, &loss))) return rc;
+            if ((rc = train_step_result(call, loss_rows, cfg->detect_anomaly != 0, epoch, nbatches, &loss))) return rc;
             avgloss += loss;
             ++nbatches;
         }
@@ -750,6 +780,34 @@ int kh_train(kh_engine* e, const float* inputs, const float* obs_p, const float*
     if ((rc = train_finish(e, call, trajectories, cfg->epochs))) return rc;
     if (first_loss) *first_loss = firstloss;
     if (last_loss) *last_loss = lastloss;
+    return KH_OK;
+}
+
+int kh_train_config_check(const kh_train_config* cfg)
+{
+    if (!cfg) return fail(KH_ERR_INVALID, "null kh_train_config");
+    if (cfg->batch < 2) return fail(KH_ERR_INVALID, "batch %d: batch >= 2 required", (int)cfg->batch);
+    if (cfg->epochs < 1) return fail(KH_ERR_INVALID, "epochs %d: epochs >= 1 required", (int)cfg->epochs);
+    const struct { const char* name; float v; } reals[3] = { { "momentum", cfg->momentum }, { "weight_decay", cfg->weight_decay },
+                                                             { "max_grad_norm", cfg->max_grad_norm } };
+    for (const auto& r : reals) {
+        if (!std::isfinite(r.v)) return fail(KH_ERR_INVALID, "%s is not finite", r.name);
+        if (r.v < 0.0f) return fail(KH_ERR_INVALID, "%s %g: must not be negative", r.name, (double)r.v);
+    }
+    if (cfg->momentum >= 1.0f) return fail(KH_ERR_INVALID, "momentum %g outside [0, 1)", (double)cfg->momentum);
+    if (cfg->nesterov != 0 && cfg->nesterov != 1) return fail(KH_ERR_INVALID, "nesterov %d: 0 or 1 required", (int)cfg->nesterov);
+    if (cfg->nesterov && cfg->momentum == 0.0f) return fail(KH_ERR_INVALID, "nesterov requires momentum > 0");
+    return KH_OK;
+}
+
+int kh_train_grad_norms(kh_engine* e, float* norms, int cap, int* steps)
+{
+    if (!e || !steps || cap < 0 || (cap > 0 && !norms)) return fail(KH_ERR_INVALID, "kh_train_grad_norms: an engine, steps and a buffer for cap norms required");
+    std::lock_guard<std::mutex> lk(e->train_mu);
+    const std::vector<float> none;
+    const std::vector<float>& v = e->train ? e->train->last_norms : none;
+    *steps = (int)v.size();
+    for (int i = 0; i < cap && i < (int)v.size(); ++i) norms[i] = v[i];
     return KH_OK;
 }
 

@@ -2,7 +2,8 @@
 // (nn.cpp:59-91) in TRAINING mode — BatchNorm on batch statistics with the running statistics
 // updated (momentum 0.1, unbiased variance), the reference's loss (nn.cpp:93-105)
 //     L = -sum(obs_p * log(p + 0.001)) + mean((v - obs_v)^2)      (v is [B,256], obs_v broadcasts: Q10)
-// and plain SGD p -= lr * dL/dp.
+// and plain SGD p -= lr * dL/dp, or with kh_train_config's optimizer options (momentum, Nesterov, L2 decay, gradient-norm
+// clipping) the fused update of opt_update_kernel.
 //
 // First correct path: fp32 VALU kernels, one launch per operation, every
 // reduction done by one workgroup in a fixed order (deterministic).  At the reference's batch of 8
@@ -14,10 +15,12 @@
 // layout (the BatchNorm running-statistics slots stay zero), so SGD is one axpy over the blob.
 // Activations are [B][64][C] fp32 channels-last like forward_simple.hip.
 #include "kh_internal.h"
+#include "train_opt.h"
 #include "blob_layout.h"
 
 #include <algorithm>
 #include <cstdlib>
+#include <string>
 #include <vector>
 
 namespace kh {
@@ -538,6 +541,109 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, const f
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) p[i] = fmaf(-lr, g[i], p[i]);
 }
 
+// ---- optimizer options (kh_train_config: momentum, nesterov, weight_decay, max_grad_norm) ----------------------
+// The global gradient norm, deterministic: stage 1 cuts G into gridDim.x fixed, contiguous ranges of whole float4s (the
+// grid depends on the blob size alone: opt_norm_blocks) and sums each range's squares in a fixed order — a thread's
+// float4s ascending in fp32, then lanes, then waves in double; stage 2 adds the partial sums in index order.  G covers
+// the whole blob: its running-statistics slots are zero (train_step clears G and no kernel writes them), and adding
+// +0.0 changes no bit, so this is the sum over the trainable entries.
+constexpr int OPT_NORM_MAX_BLOCKS = 1024;
+inline int opt_norm_blocks(size_t n) { const size_t b = (n + 4095) / 4096; return (int)(b < 1 ? 1 : (b > OPT_NORM_MAX_BLOCKS ? OPT_NORM_MAX_BLOCKS : b)); }
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, long n, double* __restrict__ part)
+{
+    __shared__ double red[4];
+    const long n4 = n >> 2, per = (n4 + gridDim.x - 1) / gridDim.x;
+    const long lo = (long)blockIdx.x * per, hi = lo + per < n4 ? lo + per : n4;
+    const float4* __restrict__ g4 = reinterpret_cast<const float4*>(g);
+    float s = 0.0f;
+    for (long i = lo + threadIdx.x; i < hi; i += 256) {
+        const float4 v = g4[i];
+        s = fmaf(v.x, v.x, s); s = fmaf(v.y, v.y, s); s = fmaf(v.z, v.z, s); s = fmaf(v.w, v.w, s);
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0)                   // the n & 3 floats behind the last float4
+        for (long i = n4 * 4; i < n; ++i) s = fmaf(g[i], g[i], s);
+    double d = (double)s;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) d += __shfl_xor(d, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = d;
+    __syncthreads();
+    if (threadIdx.x == 0) part[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// one workgroup: out[0] = norm, out[1] = c = min(1, max_norm / (norm + 1e-6))    (clip_grad_norm_'s coefficient)
+__global__ __launch_bounds__(256) void grad_norm_kernel(const double* __restrict__ part, int nparts, float max_norm, float* __restrict__ out)
+{
+    __shared__ double ps[OPT_NORM_MAX_BLOCKS];
+    for (int i = threadIdx.x; i < nparts; i += 256) ps[i] = part[i];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = 0.0;
+        for (int i = 0; i < nparts; ++i) s += ps[i];
+        const float norm = (float)sqrt(s);
+        out[0] = norm;
+        out[1] = fminf(1.0f, max_norm / (norm + 1e-6f));
+    }
+}
+
+// Steps 1-5 of kami_hip.h's update rule in one pass over the blob: reads p, g (v), writes p (v), 16 bytes per thread and
+// access, grid-strided over tiles of 1024 floats.  `frozen`: the running-statistics slots (TrainNet::frozen, ascending
+// disjoint [lo, hi) pairs) — a tile that meets none of them, nearly every tile, takes the float4 path; the others and
+// the blob's short last tile go element by element and leave the frozen entries of p and v alone.
+constexpr int OPT_TILE = 1024;
+struct OptArgs { float lr, mu, wd; int nesterov; };
+__device__ __forceinline__ void opt_update_one(float& p, float g, float& v, float c, bool clip, const OptArgs& a)
+{
+    if (clip) g *= c;
+    if (a.wd != 0.0f) g = fmaf(a.wd, p, g);
+    float d = g;
+    if (a.mu != 0.0f) {
+        v = fmaf(a.mu, v, g);
+        d = a.nesterov ? fmaf(a.mu, v, g) : v;
+    }
+    p = fmaf(-a.lr, d, p);
+}
+
+__global__ __launch_bounds__(256) void opt_update_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ v, long n,
+                                                         const long long* __restrict__ frozen, int nfrozen,
+                                                         const float* __restrict__ clip_c /* null: no clipping */, OptArgs a)
+{
+    const bool clip = clip_c != nullptr, mom = a.mu != 0.0f;
+    const float c = clip ? clip_c[0] : 1.0f;
+    const long ntiles = (n + OPT_TILE - 1) / OPT_TILE;
+    for (long t = blockIdx.x; t < ntiles; t += gridDim.x) {
+        const long t_lo = t * OPT_TILE, t_hi = t_lo + OPT_TILE < n ? t_lo + OPT_TILE : n;
+        int f0 = 0, f1 = nfrozen;                           // the first frozen range that ends behind the tile's start
+        while (f0 < f1) {
+            const int m = (f0 + f1) >> 1;
+            if (frozen[2 * m + 1] > t_lo) f1 = m; else f0 = m + 1;
+        }
+        const bool mixed = (f0 < nfrozen && frozen[2 * f0] < t_hi) || t_hi - t_lo < OPT_TILE;
+        const long i = t_lo + 4 * (long)threadIdx.x;
+        if (!mixed) {
+            float4 pv = *reinterpret_cast<const float4*>(p + i);
+            const float4 gv = *reinterpret_cast<const float4*>(g + i);
+            float4 vv = mom ? *reinterpret_cast<const float4*>(v + i) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            opt_update_one(pv.x, gv.x, vv.x, c, clip, a);
+            opt_update_one(pv.y, gv.y, vv.y, c, clip, a);
+            opt_update_one(pv.z, gv.z, vv.z, c, clip, a);
+            opt_update_one(pv.w, gv.w, vv.w, c, clip, a);
+            *reinterpret_cast<float4*>(p + i) = pv;
+            if (mom) *reinterpret_cast<float4*>(v + i) = vv;
+        } else {
+            for (long e = i; e < i + 4 && e < t_hi; ++e) {
+                bool fr = false;
+                for (int f = f0; f < nfrozen && frozen[2 * f] < t_hi; ++f) fr = fr || (e >= frozen[2 * f] && e < frozen[2 * f + 1]);
+                if (fr) continue;
+                float pe = p[e], ve = mom ? v[e] : 0.0f;
+                opt_update_one(pe, g[e], ve, c, clip, a);
+                p[e] = pe;
+                if (mom) v[e] = ve;
+            }
+        }
+    }
+}
+
 inline int nblocks(long total) { long b = (total + 255) / 256; return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b)); }
 
 struct ConvBNOff { size_t w, b, g, be, rm, rv; int Ci, Co, T; };
@@ -549,6 +655,7 @@ struct TrainNet {
     ConvBNOff stem, pconv, vconv;
     std::vector<ConvBNOff> res;
     size_t p2w, p2b, fcw, fcb, total;
+    std::vector<long long> frozen;       // the running_mean / running_var slots, [lo, hi) pairs ascending: what no update may touch
 };
 
 static TrainNet layout(int F, int C, int R)
@@ -572,6 +679,11 @@ static TrainNet layout(int F, int C, int R)
     n.vconv = convbn();
     n.fcw = take(); n.fcb = take();
     n.total = kh_blob::total(L);
+    for (const kh_blob::Tensor& t : L) {
+        if (t.name.find(".running_") == std::string::npos) continue;
+        if (!n.frozen.empty() && n.frozen.back() == (long long)t.at) n.frozen.back() = (long long)(t.at + t.n);   // running_var follows running_mean
+        else { n.frozen.push_back((long long)t.at); n.frozen.push_back((long long)(t.at + t.n)); }
+    }
     return n;
 }
 
@@ -614,9 +726,11 @@ size_t train_workspace_floats(int F, int C, int R, int B)
     return n;
 }
 
-hipError_t train_step(const TrainNet& n, const StepBuffers& sb, const float* x_in, const float* obsp, const float* obsv,
-                      int B, float lr, float* loss_rows /* [2*B] device: policy rows, value squared-error rows; behind them two ints:
-                      a policy / value output of this step's forward is NaN */, hipStream_t s)
+static hipError_t step_impl(const TrainNet& n, const StepBuffers& sb, const OptBuffers* ob /* null: plain SGD */, const float* x_in,
+                            const float* obsp, const float* obsv, int B, const StepOpt& opt,
+                            float* loss_rows /* [2*B] device: policy rows, value squared-error rows; behind them two ints: a policy /
+                            value output of this step's forward is NaN; behind those, with max_grad_norm > 0, the gradient norm
+                            before clipping and the clip factor */, hipStream_t s)
 {
     int* nanflags = reinterpret_cast<int*>(loss_rows + 2 * B);
     (void)hipMemsetAsync(nanflags, 0, 2 * sizeof(int), s);
@@ -766,11 +880,39 @@ hipError_t train_step(const TrainNet& n, const StepBuffers& sb, const float* x_i
     }
     bwd(n.stem, sv[0], dX, dtmp, nullptr, 0);
 
-    hipLaunchKernelGGL(sgd_kernel, dim3(nblocks((long)n.total)), dim3(256), 0, s, P, G, lr, (long)n.total);
+    if (!ob) {                                          // the reference's rule, the graph every earlier version recorded
+        hipLaunchKernelGGL(sgd_kernel, dim3(nblocks((long)n.total)), dim3(256), 0, s, P, G, opt.lr, (long)n.total);
+        return hipGetLastError();
+    }
+    float* clip_out = nullptr;                          // norm, c: device memory, read by the update without a host round trip
+    if (opt.max_grad_norm > 0.0f) {
+        clip_out = loss_rows + 2 * B + 2;
+        const int nb = opt_norm_blocks(n.total);
+        hipLaunchKernelGGL(grad_sumsq_kernel, dim3(nb), dim3(256), 0, s, G, (long)n.total, ob->norm_part);
+        hipLaunchKernelGGL(grad_norm_kernel, dim3(1), dim3(256), 0, s, ob->norm_part, nb, opt.max_grad_norm, clip_out);
+    }
+    const long ntiles = ((long)n.total + OPT_TILE - 1) / OPT_TILE;
+    hipLaunchKernelGGL(opt_update_kernel, dim3((int)(ntiles > 4096 ? 4096 : ntiles)), dim3(256), 0, s, P, G, ob->vel, (long)n.total,
+                       ob->frozen, (int)(n.frozen.size() / 2), clip_out ? clip_out + 1 : nullptr,
+                       OptArgs{ opt.lr, opt.momentum, opt.weight_decay, opt.nesterov });
     return hipGetLastError();
 }
 
+hipError_t train_step(const TrainNet& n, const StepBuffers& sb, const float* x_in, const float* obsp, const float* obsv,
+                      int B, float lr, float* loss_rows, hipStream_t s)
+{
+    return step_impl(n, sb, nullptr, x_in, obsp, obsv, B, StepOpt{ lr, 0.0f, 0.0f, 0.0f, 0 }, loss_rows, s);
+}
+
+hipError_t train_step_opt(const TrainNet& n, const StepBuffers& sb, const OptBuffers& ob, const float* x_in, const float* obsp,
+                          const float* obsv, int B, const StepOpt& opt, float* loss_rows, hipStream_t s)
+{
+    return step_impl(n, sb, &ob, x_in, obsp, obsv, B, opt, loss_rows, s);
+}
+
 TrainNet* train_layout_new(int F, int C, int R) { return new TrainNet(layout(F, C, R)); }
+size_t train_frozen_ranges(const TrainNet& n, const long long** ranges) { *ranges = n.frozen.data(); return n.frozen.size() / 2; }
+size_t train_norm_parts(size_t blob_floats) { return (size_t)opt_norm_blocks(blob_floats); }
 void train_layout_free(TrainNet* n) { delete n; }
 
 }  // namespace kh

@@ -194,6 +194,7 @@ int kh_train_records(kh_engine* e, const kh_record* rec, int n, const kh_train_c
     if (n < 1 || cfg->batch < 2 || cfg->epochs < 1) return fail(KH_ERR_INVALID, "trajectories >= 1, batch >= 2, epochs >= 1 required");
     int rc = check_records(e, "kh_train_records");
     if (rc) return rc;
+    if ((rc = kh_train_config_check(cfg))) return rc;
     if ((rc = records_check(rec, n, nullptr))) return rc;
     TrainCall call;
     if ((rc = train_begin(e, cfg, "kh_train_records", call))) return rc;
@@ -201,7 +202,7 @@ int kh_train_records(kh_engine* e, const kh_record* rec, int n, const kh_train_c
     hipStream_t st = call.st;
     const int B = cfg->batch, epochs = cfg->epochs;
     const int per_epoch = (n + B - 1) / B;
-    const size_t nsteps = (size_t)epochs * per_epoch, slot = (size_t)B * 2 + 2;      // floats of one step's dloss block
+    const size_t nsteps = (size_t)epochs * per_epoch, slot = kh::train_result_floats(B);      // floats of one step's dloss block
 
     // records and order through one page-locked block, one copy each; the order is kh_train's (kh_train_order)
     const RecordBlock lay((size_t)n);
@@ -227,7 +228,7 @@ int kh_train_records(kh_engine* e, const kh_record* rec, int n, const kh_train_c
             launch_expand_records(tc.rec.as<char>(), lay, tc.order.as<int32_t>() + (size_t)epoch * n, base, std::min(B, n - base),
                                   tc.dx.as<float>(), tc.dp.as<float>(), tc.dv.as<float>(), st);
             HIPCHK(hipGetLastError());
-            if ((rc = train_launch_step(call, cfg->lr))) return rc;
+            if ((rc = train_launch_step(call))) return rc;
             HIPCHK(hipMemcpyAsync(slots + step * slot, tc.dloss.p, slot * 4, hipMemcpyDeviceToHost, st));
         }
     HIPCHK(hipStreamSynchronize(st));                         // the one synchronisation of the call
@@ -239,7 +240,7 @@ int kh_train_records(kh_engine* e, const kh_record* rec, int n, const kh_train_c
         float avgloss = 0.0f;
         for (int b = 0; b < per_epoch; ++b, ++step) {
             float loss;
-            if ((rc = train_step_result(slots + step * slot, B, cfg->detect_anomaly != 0, epoch, b, &loss))) return rc;
+            if ((rc = train_step_result(call, slots + step * slot, cfg->detect_anomaly != 0, epoch, b, &loss))) return rc;
             avgloss += loss;
         }
         avgloss /= (float)per_epoch;

@@ -36,12 +36,14 @@ def records_to_arrays(nn, records):
 
 
 def generation(nn, pool, replay: "ReplayBuffer | CompactReplay", *, play_evals: int, play_seconds: float = 60.0, sample: int | None = None,
-               mlr: int = 5, epochs: int = 8, batchsize: int = 8, dist=None, device: str | None = None, gate: dict | None = None):
+               mlr: int = 5, epochs: int = 8, batchsize: int = 8, momentum: float = 0.0, nesterov: bool = False,
+               weight_decay: float = 0.0, max_grad_norm: float = 0.0, dist=None, device: str | None = None, gate: dict | None = None):
     """Play, collect, train (rank 0), publish.  Returns a dict of what happened.  The collectives' tensors live where
     the group's backend needs them (kd.collective_device: device memory for RCCL, host memory for gloo).
     gate=None: the trained weights are installed unconditionally.  gate=dict(...): rank 0 trains a clone of `nn`, plays
     search.Match(nn, clone, **gate) and installs the clone's weights and generation on `nn` only if it is accepted
-    (selfplay.cpp:259-287); the result gains accepted, gate_score, gate_games."""
+    (selfplay.cpp:259-287); the result gains accepted, gate_score, gate_games.
+    momentum / nesterov / weight_decay / max_grad_norm: NN.train's optimizer options, passed to either training path."""
     device = device or kd.collective_device(dist)
     import ctypes as C
     from . import search as S
@@ -76,16 +78,17 @@ def generation(nn, pool, replay: "ReplayBuffer | CompactReplay", *, play_evals: 
     out = {"evals": st.evals, "games_finished": st.games_finished, "records": len(vals), "merged": merged,
            "generation_before": nn.get_generation()}
     have = min(replay.count(), replay.size())
+    optim = dict(momentum=momentum, nesterov=nesterov, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
     trainee = nn.clone() if gate is not None and rank == 0 and have >= batchsize else nn      # selfplay.cpp:259
     if rank == 0 and have >= batchsize and compact:
         n = sample or (have // batchsize) * batchsize
-        first, last = trainee.train_records(replay.select(n), mlr=mlr, epochs=epochs, batchsize=batchsize)
+        first, last = trainee.train_records(replay.select(n), mlr=mlr, epochs=epochs, batchsize=batchsize, **optim)
         out.update(first_loss=first, last_loss=last, trained_on=n)
     elif rank == 0 and have >= batchsize:
         n = sample or (have // batchsize) * batchsize
         src = replay._rng.integers(0, have, n)                               # replaybuffer.h:61-84, over the written slots
         first, last = trainee.train(replay.input_buffer[src].reshape(n, 8, 8, 30), replay.mcts_buffer[src], replay.result_buffer[src],
-                               mlr=mlr, epochs=epochs, batchsize=batchsize)
+                               mlr=mlr, epochs=epochs, batchsize=batchsize, **optim)
         out.update(first_loss=first, last_loss=last, trained_on=n)
     if gate is not None:
         out.update(accepted=False, gate_score=0.0, gate_games=0)             # (nothing trained, or not the training rank)

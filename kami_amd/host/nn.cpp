@@ -179,7 +179,9 @@ void NN::infer(float* input, int batch, float* policy, float* value)
     if (rc) raise(rc);
 }
 
-// nn.cpp:236-238: the three option keys the reference reads
+// nn.cpp:236-238: the three option keys the reference reads, and four of this engine's for kh_train_config's optimizer
+// fields — integers like training_mlr, all 0 by default (the reference's plain SGD): training_momentum_pct (/ 100),
+// training_nesterov (0 / 1), training_weight_decay_ppm (x 1e-6), training_max_grad_mnorm (/ 1000)
 static kh_train_config train_options(bool detect_anomaly)
 {
     kh_train_config cfg;
@@ -188,6 +190,10 @@ static kh_train_config train_options(bool detect_anomaly)
     cfg.epochs = options::getInt("training_epochs", 8);
     cfg.batch = options::getInt("training_batchsize", 8);
     cfg.detect_anomaly = detect_anomaly ? 1 : 0;                 // nn.cpp:231-232,329-344: the same three messages
+    cfg.momentum = (float)options::getInt("training_momentum_pct", 0) / 100.0f;
+    cfg.nesterov = options::getInt("training_nesterov", 0);
+    cfg.weight_decay = (float)options::getInt("training_weight_decay_ppm", 0) * 1e-6f;
+    cfg.max_grad_norm = (float)options::getInt("training_max_grad_mnorm", 0) / 1000.0f;
     return cfg;
 }
 

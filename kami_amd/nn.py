@@ -179,33 +179,54 @@ class NN:
     def get_generation(self) -> int:
         return self._lib.kh_generation(self._h)
 
+    @staticmethod
+    def _train_config(mlr, epochs, batchsize, detect_anomaly, momentum, nesterov, weight_decay, max_grad_norm):
+        return L.TrainConfig(mlr / 1000.0, epochs, batchsize, 1 if detect_anomaly else 0,
+                             momentum, weight_decay, max_grad_norm, 1 if nesterov else 0)
+
     def train(self, inputs: np.ndarray, obs_p: np.ndarray, obs_v: np.ndarray, *, mlr: int = 5, epochs: int = 8,
-              batchsize: int = 8, detect_anomaly: bool = False):
+              batchsize: int = 8, detect_anomaly: bool = False, momentum: float = 0.0, nesterov: bool = False,
+              weight_decay: float = 0.0, max_grad_norm: float = 0.0):
         """NN::train (nn.cpp:224-377) on the device; option names and defaults of nn.cpp:236-238.
         Returns (average loss of the first epoch, of the last epoch); the generation goes up by one.
         detect_anomaly (nn.cpp:231-232,329-344): every batch's input and the forward's two outputs are checked for NaN,
-        and the call fails with the reference's messages."""
+        and the call fails with the reference's messages.
+        momentum / nesterov / weight_decay / max_grad_norm (all off by default: the reference's plain SGD): what
+        clip_grad_norm_(params, max_grad_norm) followed by torch.optim.SGD(lr, momentum, 0, weight_decay, nesterov).step()
+        does, with a velocity that lives for this call (kami_hip.h, kh_train_config); last_grad_norms() has the norms."""
         x = np.ascontiguousarray(inputs, dtype=np.float32)
         p = np.ascontiguousarray(obs_p, dtype=np.float32)
         v = np.ascontiguousarray(obs_v, dtype=np.float32)
         n = x.shape[0]
         assert p.shape == (n, PSIZE) and v.shape == (n,)
-        cfg = L.TrainConfig(mlr / 1000.0, epochs, batchsize, 1 if detect_anomaly else 0)
+        cfg = self._train_config(mlr, epochs, batchsize, detect_anomaly, momentum, nesterov, weight_decay, max_grad_norm)
         first, last = C.c_float(), C.c_float()
         _chk(self._lib.kh_train(self._h, x.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p),
                                 v.ctypes.data_as(C.c_void_p), n, C.byref(cfg), C.byref(first), C.byref(last)))
         self._blob = self.get_weights()
         return first.value, last.value
 
-    def train_records(self, records, *, mlr: int = 5, epochs: int = 8, batchsize: int = 8, detect_anomaly: bool = False):
+    def train_records(self, records, *, mlr: int = 5, epochs: int = 8, batchsize: int = 8, detect_anomaly: bool = False,
+                      momentum: float = 0.0, nesterov: bool = False, weight_decay: float = 0.0, max_grad_norm: float = 0.0):
         """kh_train_records: train() on compact records (as_records: ctypes, bytes or NumPy), expanded per batch on the
-        device — the same result as train(*expand_records(records)), bit for bit, without the dense arrays."""
+        device — the same result as train(*expand_records(records)) with the same options, bit for bit, without the dense
+        arrays."""
         rec = as_records(records)
-        cfg = L.TrainConfig(mlr / 1000.0, epochs, batchsize, 1 if detect_anomaly else 0)
+        cfg = self._train_config(mlr, epochs, batchsize, detect_anomaly, momentum, nesterov, weight_decay, max_grad_norm)
         first, last = C.c_float(), C.c_float()
         _chk(self._lib.kh_train_records(self._h, _ptr(rec), rec.size, C.byref(cfg), C.byref(first), C.byref(last)))
         self._blob = self.get_weights()
         return first.value, last.value
+
+    def last_grad_norms(self) -> np.ndarray:
+        """kh_train_grad_norms: the gradient norm before clipping of every step of the last completed train() /
+        train_records() call that ran with max_grad_norm > 0, in step order (empty if it did not clip)."""
+        steps = C.c_int(0)
+        _chk(self._lib.kh_train_grad_norms(self._h, None, 0, C.byref(steps)))
+        out = np.empty(steps.value, np.float32)
+        if steps.value:
+            _chk(self._lib.kh_train_grad_norms(self._h, _ptr(out), out.size, C.byref(steps)))
+        return out[:steps.value]
 
     def expand_records(self, records):
         """kh_expand_records: -> (planes [n,8,8,30], obs_p [n,4672], obs_v [n]), the dense arrays train() takes."""

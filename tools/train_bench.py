@@ -4,7 +4,10 @@ call's fixed work — workspace, parameter upload, recording the step graph, ins
 `marginal`: (t(4 epochs) - t(2 epochs)) / extra steps: what one more SGD step costs.
 
 `python tools/train_bench.py records [alternations]`: the record path (kh_train_records) against the dense path (kh_train)
-on the same samples, whole calls alternated within one process and one engine; see records_leg()."""
+on the same samples, whole calls alternated within one process and one engine; see records_leg().
+
+`python tools/train_bench.py optimizer [alternations]`: plain SGD calls alternated with calls that use every optimizer
+option (momentum, Nesterov, L2 decay, clipping) in one process; see optimizer_leg()."""
 import sys, os, time
 sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
 import numpy as np
@@ -71,6 +74,45 @@ def records_leg(alternations=5):
               f"  host -> device per call: dense {steps * tb * 26372:,} B staged, records {n * 664 + epochs * n * 4:,} B", flush=True)
         nn.close()
 
+
+def optimizer_leg(alternations=7):
+    """Per shape two engines in one process, one trained with plain SGD and one with all four optimizer options (so
+    neither re-records its step graph), calls alternated plain / optimizer from the same starting weights.  A step's
+    cost is the difference of a 4-epoch and a 2-epoch call over the extra steps (the calls' fixed work cancels), host
+    clock around the calls; min / median / max over the alternations after one warm-up round."""
+    opts = dict(momentum=0.9, nesterov=True, weight_decay=1e-4, max_grad_norm=1.0)
+    for C_, R, tb, n in ((64, 6, 8, 256), (256, 20, 32, 128)):
+        blob = W.random_weights(30, C_, R, seed=1)
+        x = rng.random((n, 8, 8, 30), dtype=np.float32)
+        p = np.zeros((n, 4672), np.float32); p[np.arange(n), rng.integers(0, 4672, n)] = 1.0
+        v = rng.choice(np.array([-1, 0, 1], np.float32), n)
+        legs = {"plain": (NN(8, 8, 30, 4672, filters=C_, residuals=R, dtype="bf16"), {}),
+                "optimizer": (NN(8, 8, 30, 4672, filters=C_, residuals=R, dtype="bf16"), opts)}
+        per_step = {k: [] for k in legs}
+        extra = 2 * (n // tb)
+        for it in range(alternations + 1):                         # the first round is the warm-up
+            for name, (nn, kw) in legs.items():
+                dt = []
+                for epochs in (2, 4):
+                    nn.load_weights(blob, 0)
+                    t0 = time.perf_counter()
+                    nn.train(x, p, v, epochs=epochs, batchsize=tb, **kw)
+                    dt.append(time.perf_counter() - t0)
+                if it:
+                    per_step[name].append((dt[1] - dt[0]) / extra)
+        norms = legs["optimizer"][0].last_grad_norms()
+        fmt = lambda a: "%7.3f /%7.3f /%7.3f ms" % (1e3 * min(a), 1e3 * float(np.median(a)), 1e3 * max(a))
+        print(f"{R}x{C_} F=30 batch {tb} n {n}: per step, min / median / max over {alternations} alternations "
+              f"({blob.size:,} parameters; {int((norms > opts['max_grad_norm']).sum())} of {norms.size} steps of the last call clipped):\n"
+              f"  plain SGD     {fmt(per_step['plain'])}\n"
+              f"  all options   {fmt(per_step['optimizer'])}", flush=True)
+        for nn, _ in legs.values():
+            nn.close()
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "optimizer":
+    optimizer_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 7)
+    sys.exit(0)
 
 if len(sys.argv) > 1 and sys.argv[1] == "records":
     records_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 5)
