@@ -174,7 +174,7 @@ __device__ __forceinline__ void ring_issue(const char* stream, int nch, int c, i
 // that is already in registers (AHEAD), so its reads must have completed before the step's barrier.
 // NP = passes over the input channels, CPT * 64 of them each: the image of one pass is 1/NP the size (256
 // channels as 2 x 128: two workgroups per CU there too; passes of 64 channels: image + ring = 50 944 B, THREE
-// workgroups per CU at 168 registers).  Weights are packed in 64-channel slices (kh_api.hip: pack_layer_generic),
+// workgroups per CU at 168 registers).  Weights are packed in 64-channel slices (weights_pack.h: PK_BLOCKS, CBC 64),
 // the order every variant walks (chunk_off).
 template <typename T, int TAPS, int EPI, int CPT, int RDN = RD, int NP = 1>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, RDN == 2 ? (CPT == 1 ? 3 : 2) : 1))) void conv_mfma_kernel(ConvArgs a)
@@ -395,7 +395,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, RDN == 2
 // straight from registers to HBM (16-byte stores after a v_permlane32_swap of packed pairs, no transpose tile).
 // Same reduction order as conv_mfma_kernel (64-channel slices outermost, then taps, then k-steps), same fp32
 // epilogue: the two kernels agree bit for bit and the launcher picks per call.
-// Weights: pack_layer_wide128 (kh_api.hip): [Co/128][Ci/64][tap][half][ks2][ms 0..3][lane][8], 8 KB chunks.
+// Weights: PK_BLOCKS at CBC 128 (weights_pack.h): [Co/128][Ci/64][tap][half][ks2][ms 0..3][lane][8], 8 KB chunks.
 template <typename T, int EPI, int NP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) void conv4_mfma_kernel(ConvArgs a)
 {
@@ -565,7 +565,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // through all (1 + 2R) x 36 chunks.  Same reduction order and epilogue arithmetic as the per-layer kernels: same bits.
 struct Head4Args {
     const unsigned short* x;      // T [B][64][Ci], Ci = NP * 128
-    const unsigned short* w;      // policyconv chunks (Ci / 32 of 8 KB) then policyconv2 chunks (4), pack_layer_wide128 order
+    const unsigned short* w;      // policyconv chunks (Ci / 32 of 8 KB) then policyconv2 chunks (4), PK_BLOCKS order at CBC 128
     const float* shift1;          // [128] folded pbatchnorm shift
     const float* bias2;           // [128] policyconv2 bias, planes >= 73 zero
     float* policy;                // [B][4672]
@@ -599,7 +599,7 @@ struct Tower128Args {
     int F;                        // planes per pixel, <= 128
     unsigned magic;               // ceil(2^32 / F): e / F = umulhi(e, magic) for e < 64 * 128
     const unsigned short* in;     // T [B][64][128]: the planes, converted and zero-padded (planes_to_act_kernel)
-    const unsigned short* w;      // (1 + 2R) layers x 36 chunks of 8 KB, pack_layer_wide128 order (Co = Ci = 128)
+    const unsigned short* w;      // (1 + 2R) layers x 36 chunks of 8 KB, PK_BLOCKS order at CBC 128 (Co = Ci = 128)
     const float* shift;           // (1 + 2R) x 128 folded BatchNorm shifts
     unsigned short* out;          // T [B][64][128]: the residual stream after the last block (HEAD: not written)
     int B, R;
@@ -1014,7 +1014,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 // B fragments (16 KB per step for the workgroup, a quarter of its bandwidth): no ring, no LDS-DMA, no barrier inside a
 // layer.  A layer boundary is two workgroup barriers (everybody has read the old image; everybody has written its 64
 // channels of the new one) around tower128's epilogue.  The stem has 128 (padded) input planes = 72 k-steps, the other
-// layers 144.  Weights: pack_layer_wide128(..., CBC = 256): [Ci/64][tap][k-step][row tile 0..7][lane][8] — the
+// layers 144.  Weights: PK_BLOCKS at CBC 256 (weights_pack.h): [Ci/64][tap][k-step][row tile 0..7][lane][8] — the
 // per-layer kernels' reduction order, so the same bits.
 struct Tower256Args {
     const float* planes;          // fp32 [B][64][F], F <= 128, 16-byte aligned

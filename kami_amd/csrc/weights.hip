@@ -1,8 +1,9 @@
 // weights.hip — parameter sets: the canonical blob parsed (blob_layout.h), BatchNorm folded into the layers' epilogues,
 // the weights packed into each kernel family's fragment order (forward_simple.hip, tower8_mfma.hip, layers_mfma.hip),
-// and the result installed as the engine's current set.  What goes where is planned once (plan_set); a blob in host
-// memory is packed by the loops below and uploaded (kh_load_weights, checkpoints, kh_clone), a blob in device memory by
-// the kernels of weights_pack.hip (kh_load_weights_device, kh_train's result) — the same bits either way.
+// and the result installed as the engine's current set.  What goes where is planned once (plan_set), as the jobs of
+// weights_pack.h, and bound to one of two memories: a blob in host memory is packed by run_host's loops over that
+// header's layout functions and uploaded (kh_load_weights, checkpoints, kh_clone), a blob in device memory by the kernels
+// of weights_pack.hip over the same functions (kh_load_weights_device, kh_train's result).
 #include "engine.h"
 #include "blob_layout.h"
 #include "weights_pack.h"
@@ -47,122 +48,11 @@ HostNet parse_blob(const float* blob, int F, int C, int R)
     return n;
 }
 
-// Eval-mode BatchNorm folded to an epilogue (scale, shift):
-//   bn(conv + bias) = conv * s + ((bias - mean) * s + beta),  s = gamma / sqrt(var + 1e-5)
-void fold_bn(const ConvBN& c, int co, float* scale, float* shift)
-{
-    for (int i = 0; i < co; ++i) {
-        const float s = c.g[i] / sqrtf(c.rv[i] + 1e-5f);
-        scale[i] = s;
-        shift[i] = (c.b[i] - c.rm[i]) * s + c.be[i];
-    }
-}
-
-// Append one layer's MFMA A-operand fragments (v_mfma_f32_32x32x16: lane l = (r = l & 31, h = l >> 5)
-// holds W[co = ms*32 + r][k = 8h + j], j = 0..7) in consumption order tap -> k-step -> ms, BN scale
-// folded in before rounding, zero-padded to (MS*32, KS*16).
-// ci0: first input channel of this pass (the 33..128-plane stem runs as four 32-channel passes).
-// centre_first: 3x3 taps in the order 4,0,1,2,3,5,6,7,8.  perm: the first `perm` k-steps of the
-// stream take their activations from the consumer's packed output registers (tower_common.h,
-// packed_fragments): slot (h, j) of k-step ks is input channel
-// 32 (ks >> 1) + 8 (2 (ks & 1) + (j >> 2)) + 4 h + (j & 3) instead of 16 ks + 8 h + j.
-void pack_layer(std::vector<uint16_t>& out, int dtype, const float* w, const float* scale, int Co, int Ci,
-                int taps, int KS, int MS, int ci0 = 0, bool centre_first = false, int perm = 0)
-{
-    int kstep = 0;
-    for (int ti = 0; ti < taps; ++ti) {
-        const int tap = !centre_first ? ti : (ti == 0 ? 4 : (ti <= 4 ? ti - 1 : ti));
-        for (int ks = 0; ks < KS; ++ks, ++kstep)
-            for (int ms = 0; ms < MS; ++ms)
-                for (int l = 0; l < 64; ++l) {
-                    const int r = l & 31, h = l >> 5;
-                    for (int j = 0; j < 8; ++j) {
-                        const int co = ms * 32 + r;
-                        const int ci = ci0 + (kstep < perm ? 32 * (ks >> 1) + 8 * (2 * (ks & 1) + (j >> 2)) + 4 * h + (j & 3)
-                                                           : ks * 16 + 8 * h + j);
-                        float v = 0.0f;
-                        if (co < Co && ci < Ci) v = w[((size_t)co * Ci + ci) * taps + tap] * (scale ? scale[co] : 1.0f);
-                        out.push_back(dtype == KH_BF16 ? f2bf16(v) : f2f16(v));
-                    }
-                }
-    }
-}
-
-// Fragments of one layer for layers_mfma.hip, BN scale folded in: 8 KB chunks of 64 input channels x 64
-// output channels, [Co/64][Ci/64][tap][4][2][lane][8] — 64-channel slices of the reduction outermost, so that
-// the kernel's variants (whole image staged at once, or in passes of 64 / 128 channels) all walk the same
-// order and agree bit for bit.
-void pack_layer_generic(uint16_t* o, int dtype, const float* w, const float* scale,
-                        int Co, int Ci, int taps, int CoP, int CiP)
-{
-    // (runs at every weight install, the trainer's included: written by index into a slice sized CoP * CiP * taps)
-    const bool bf = dtype == KH_BF16;
-    for (int cb = 0; cb < CoP / 64; ++cb)
-        for (int slice = 0; slice < CiP / 64; ++slice)
-            for (int tap = 0; tap < taps; ++tap)
-                for (int kk = 0; kk < 4; ++kk)
-                    for (int ms = 0; ms < 2; ++ms)
-                        for (int l = 0; l < 64; ++l) {
-                            const int r = l & 31, h = l >> 5, ks = slice * 4 + kk;
-                            const int co = cb * 64 + ms * 32 + r, ci0 = ks * 16 + 8 * h;
-                            const float sc = scale ? (co < Co ? scale[co] : 0.0f) : 1.0f;
-                            const float* src = w + ((size_t)co * Ci + ci0) * taps + tap;
-                            for (int j = 0; j < 8; ++j) {
-                                const float v = (co < Co && ci0 + j < Ci) ? src[(size_t)j * taps] * sc : 0.0f;
-                                *o++ = bf ? f2bf16(v) : f2f16(v);
-                            }
-                        }
-}
-
-// The same fragments for conv4_mfma_kernel (four boards x 128 output channels per workgroup): 8 KB chunks of 32 input
-// channels x 128 output channels, [Co/128][Ci/64][tap][half][ks2][ms 0..3][lane][8] — the reduction walks in the same
-// order as above (64-channel slices, then taps, then k-steps), so both kernels produce the same bits.
-void pack_layer_wide128(uint16_t* o, int dtype, const float* w, const float* scale,
-                        int Co, int Ci, int taps, int CoP, int CiP, int CBC = 128)
-{
-    // CBC: output channels per block — 128 (conv4_mfma_kernel, tower128_kernel, policy_head4_kernel) or 256
-    // (tower256_kernel: eight row tiles per k-step, one k-step per 8 KB chunk)
-    const bool bf = dtype == KH_BF16;
-    for (int cb = 0; cb < CoP / CBC; ++cb)
-        for (int slice = 0; slice < CiP / 64; ++slice)
-            for (int tap = 0; tap < taps; ++tap)
-                for (int kk = 0; kk < 4; ++kk)                  // kk = 2 * half + ks2
-                    for (int ms = 0; ms < CBC / 32; ++ms)
-                        for (int l = 0; l < 64; ++l) {
-                            const int r = l & 31, h = l >> 5, ks = slice * 4 + kk;
-                            const int co = cb * CBC + ms * 32 + r, ci0 = ks * 16 + 8 * h;
-                            const float sc = scale ? (co < Co ? scale[co] : 0.0f) : 1.0f;
-                            const float* src = w + ((size_t)co * Ci + ci0) * taps + tap;
-                            for (int j = 0; j < 8; ++j) {
-                                const float v = (co < Co && ci0 + j < Ci) ? src[(size_t)j * taps] * sc : 0.0f;
-                                *o++ = bf ? f2bf16(v) : f2f16(v);
-                            }
-                        }
-}
-
-// fp32 fragments for conv_f32_kernel: [Co/64][Ci slices of <= 128][tap][slice/8][2][lane][4]; lane (r, h) holds
-// W[co = ms*32 + r][ci = 8j + 4h + 0..3]  (one slice up to 128 input channels: the image of a slice is what fits LDS)
-void pack_layer_f32(float* o, const float* w, const float* scale, int Co, int Ci, int taps, int CoP, int CiP)
-{
-    for (int cb = 0; cb < CoP / 64; ++cb)
-      for (int c_lo = 0; c_lo < CiP; c_lo += 128)
-        for (int tap = 0; tap < taps; ++tap)
-            for (int j = c_lo / 8; j < (c_lo + 128 < CiP ? c_lo + 128 : CiP) / 8; ++j)
-                for (int ms = 0; ms < 2; ++ms)
-                    for (int l = 0; l < 64; ++l) {
-                        const int r = l & 31, h = l >> 5;
-                        for (int i = 0; i < 4; ++i) {
-                            const int co = cb * 64 + ms * 32 + r, ci = j * 8 + 4 * h + i;
-                            *o++ = (co < Co && ci < Ci) ? w[((size_t)co * Ci + ci) * taps + tap] * (scale ? scale[co] : 1.0f) : 0.0f;
-                        }
-                    }
-}
-
 // ------------------------------------------------------------------------------- the plan
 // What a parameter set's serving buffers hold, stated once: every buffer's size, every layer's place and layout in it
-// and every folded parameter's, as jobs over pointers into the blob.  The pointers are only offset here, never read, so
-// the same plan describes a blob in host memory (run_host: the loops above) and one in device memory (run_device: the
-// kernels of weights_pack.hip).  The coverage decisions (tw_why, ly_ok, which extra layouts a shape gets) are made here.
+// and every folded parameter's, as jobs (weights_pack.h) over pointers into the blob.  The pointers are only offset here,
+// never read, so the same plan describes a blob in host memory (run_host) and one in device memory (run_device).  The
+// coverage decisions (tw_why, ly_ok, which extra layouts a shape gets) are made here.
 enum Buf { B_TW_STREAM, B_TW_PAR, B_TW_FC4, B_LY_W, B_LY_W4, B_LY_W2B, B_LY_WH, B_LY_SHIFT, B_LY_MISC, B_SIMPLE, NBUF };
 
 DevMem& buf_of(Weights& W, int b)
@@ -171,27 +61,13 @@ DevMem& buf_of(Weights& W, int b)
     return *m[b];
 }
 
-struct FoldItem { ConvBN c; int co; };                   // c.g == nullptr: scale 1, shift = c.b
-struct FoldRef { int item = -1, shift = 0; };            // a folded layer's scale (shift = 0) or shift (1) array
-struct PackItem {
-    int buf; size_t off, bytes;                          // where in the buffer; bytes written, padding included
-    int kind; const float* w; int fold;                  // fold: the layer whose scale is folded in (-1: none)
-    int Co, Ci, taps;
-    int KS, MS, ci0, centre_first, perm, chunk_frags;    // PK_STREAM
-    int CoP, CiP, CBC;                                   // PK_BLOCKS, PK_F32
-};
-struct CopyItem {
-    int buf; size_t off;                                 // float offset
-    int kind; const float* src; FoldRef fsrc;            // source: blob floats, or a folded array
-    int scale_of;                                        // CP_MULS: the layer whose scale[0] multiplies
-    int n, npad, Co, Ci, taps;
-};
 struct SimpleOff { size_t wt, scale, shift; int Ci, Co, taps, relu; };
 struct Plan {
     int dtype = KH_F32, fold_stride = 0;
-    std::vector<FoldItem> folds;                         // stem, 2R tower convs, policyconv, policyconv2 (bias), valueconv
-    std::vector<PackItem> packs;
-    std::vector<CopyItem> copies;
+    std::vector<FoldJob> folds;                          // stem, 2R tower convs, policyconv, policyconv2 (bias), valueconv
+    std::vector<PackJob> packs;
+    std::vector<CopyJob> copies;
+    unsigned pack_blocks = 0, copy_blocks = 0;           // workgroups of the device packer's launches (bind)
     size_t bytes[NBUF] = {};
     bool threads = false;                                // run_host: pack on several host threads (the wide nets' volumes)
     std::vector<SimpleOff> simple;
@@ -205,25 +81,41 @@ struct Plan {
     size_t fold_at(FoldRef r) const { return ((size_t)r.item * 2 + r.shift) * fold_stride; }
 };
 
+FoldJob fold_job(const ConvBN& c, int co, float* scale = nullptr, float* shift = nullptr)
+{
+    return { c.b, c.g, c.be, c.rm, c.rv, scale, shift, co };
+}
+
 void plan_folds(Plan& P, const HostNet& n, int C, int R)
 {
     P.fold_stride = std::max(C, (int)KH_POLICY_MID);
-    P.folds.push_back({ n.stem, C });
-    for (int i = 0; i < 2 * R; ++i) P.folds.push_back({ n.res[i], C });
-    P.folds.push_back({ n.pconv, KH_POLICY_MID });
-    P.folds.push_back({ ConvBN{ nullptr, n.p2b, nullptr, nullptr, nullptr, nullptr }, KH_POLICY_PLANES });
-    P.folds.push_back({ n.vconv, 1 });
+    P.folds.push_back(fold_job(n.stem, C));
+    for (int i = 0; i < 2 * R; ++i) P.folds.push_back(fold_job(n.res[i], C));
+    P.folds.push_back(fold_job(n.pconv, KH_POLICY_MID));
+    P.folds.push_back(fold_job(ConvBN{ nullptr, n.p2b, nullptr, nullptr, nullptr, nullptr }, KH_POLICY_PLANES));
+    P.folds.push_back(fold_job(n.vconv, 1));
+}
+
+// a layer's fragments at byte `off` of `buf`, `bytes` long with their padding; the caller sets the layout's own fields
+PackJob& pack_item(Plan& P, int buf, size_t off, size_t bytes, int kind, const float* w, int fold, int Co, int Ci, int taps)
+{
+    PackJob j{};
+    j.w = w; j.fold = fold; j.buf = buf; j.off = off;
+    j.groups = (unsigned)(bytes / 16);
+    j.kind = kind; j.dtype = P.dtype; j.Co = Co; j.Ci = Ci; j.taps = taps;
+    j.chunk_frags = 8;
+    P.packs.push_back(j);
+    P.bytes[buf] = std::max(P.bytes[buf], off + bytes);
+    return P.packs.back();
 }
 
 void copy_item(Plan& P, int buf, size_t off, int kind, const float* src, FoldRef fsrc, int n, int npad, int scale_of = -1,
                int Co = 0, int Ci = 0, int taps = 0)
 {
-    P.copies.push_back({ buf, off, kind, src, fsrc, scale_of, n, npad, Co, Ci, taps });
+    P.copies.push_back({ src, fsrc, scale_of, buf, off, nullptr, nullptr, (unsigned)n, (unsigned)npad, 0, kind, Co, Ci, taps });
     P.bytes[buf] = std::max(P.bytes[buf], (off + npad) * sizeof(float));
 }
 
-// valuefc.weight [256][64] -> [k/4][j][4]: thread j reads coalesced float4 (tower8_kernel; policy_head4_kernel /
-// tower128_kernel's value FC, where from the [256][64] rows every lane's 16 bytes were a cache line of their own)
 void copy_fc4(Plan& P, int buf, size_t off, const float* fcw)
 {
     copy_item(P, buf, off, CP_FC4, fcw, {}, KH_VALUE_WIDTH * 64, KH_VALUE_WIDTH * 64);
@@ -243,9 +135,9 @@ int plan_layers(Plan& P, Weights& W, const HostNet& n, int dtype, int F, int C, 
     const bool want2b = !f32 && CP == 256 && FP == 128;      // tower256_kernel's shape
     auto blocks = [&](int buf, size_t& at, int kind, const float* wt, int fold, int Co, int Ci, int taps, int CoP, int CiP, int CBC) {
         const size_t nel = (size_t)CoP * CiP * taps;
-        P.packs.push_back({ buf, at * el, nel * el, kind, wt, fold, Co, Ci, taps, 0, 0, 0, 0, 0, 8, CoP, CiP, CBC });
+        PackJob& j = pack_item(P, buf, at * el, nel * el, kind, wt, fold, Co, Ci, taps);
+        j.CiP = CiP; j.CBC = CBC;
         at += nel;
-        P.bytes[buf] = at * el;
     };
     auto add = [&](const float* wt, int fold, int Co, int Ci, int taps, int CoP, int CiP) {
         W.ly_shift_off.push_back(nshift);
@@ -302,7 +194,8 @@ int plan_tower(Plan& P, Weights& W, const HostNet& n, int F, int C, int R)
                       int chunk_frags, bool pad) {
         const size_t frags = (size_t)taps * KS * MS;
         const size_t out = chunk_frags < 8 ? frags / chunk_frags * 8 : (pad ? (frags + 7) / 8 * 8 : frags);
-        P.packs.push_back({ B_TW_STREAM, at * 2, out * FRAG * 2, PK_STREAM, w, fold, Co, Ci, taps, KS, MS, ci0, centre_first, perm, chunk_frags, 0, 0, 0 });
+        PackJob& j = pack_item(P, B_TW_STREAM, at * 2, out * FRAG * 2, PK_STREAM, w, fold, Co, Ci, taps);
+        j.KS = KS; j.MS = MS; j.ci0 = ci0; j.centre_first = centre_first; j.perm = perm; j.chunk_frags = chunk_frags;
         at += out * FRAG;
     };
     if (FP == 128) {        // four 32-plane passes in one unpadded run of 72 k-steps: the later quarters of the planes are
@@ -319,7 +212,6 @@ int plan_tower(Plan& P, Weights& W, const HostNet& n, int F, int C, int R)
     stream(n.p2w, -1, KH_POLICY_PLANES, KH_POLICY_MID, 1, KH_POLICY_MID / 16, 3, 0, false, KH_POLICY_MID / 16, 6, false);
     if (at % 4096) return fail(KH_ERR_INVALID, "internal: weight stream is not whole chunks");
     if (((at / 4096) & 1) != 0) stream(nullptr, -1, 0, 0, 1, 1, 8, 0, false, 0, 8, true);   // parity chunk (see gemm8_dummy): zeros
-    P.bytes[B_TW_STREAM] = at * 2;
 
     // tw_par: shifts of the 1 + 2R 3x3 layers [TW_CP each], policyconv shift [128], policyconv2 bias [128], valueconv
     // weight * scale [TW_CP], valueconv shift [4]
@@ -386,6 +278,9 @@ int plan_set(const kh_engine* e, Plan& P, Weights& W, const HostNet& n)
         if ((rc = plan_tower(P, W, n, F, C, R))) return rc;
         if (!W.tw_ok) rc = plan_layers(P, W, n, e->cfg.dtype, F, C, R);
     }
+    // 64 lanes decode a fragment together (pack_decode): the padding rules above make every job whole fragments
+    for (const PackJob& j : P.packs)
+        if (!rc && j.groups % 64) rc = fail(KH_ERR_INVALID, "internal: a pack job of %u groups is not whole fragments", j.groups);
     return rc;
 }
 
@@ -404,60 +299,65 @@ int alloc_buffers(Weights& W, const Plan& P)
     return KH_OK;
 }
 
-// ------------------------------------------------------------------------------- the host packer
-void fold_item(const FoldItem& f, float* scale, float* shift)
+// ------------------------------------------------------------------------------- the two packers
+// Turns every job's (buffer, offset) and FoldRef into pointers against one memory — the folded arrays at `fold`, the
+// buffers at `base` — and numbers the workgroups of the device packer's launches.  Job order is kept: find_job
+// (weights_pack.hip) searches by block0.
+void bind(Plan& P, float* fold, char* const base[NBUF])
 {
-    if (f.c.g) fold_bn(f.c, f.co, scale, shift);
-    else for (int i = 0; i < f.co; ++i) { scale[i] = 1.0f; shift[i] = f.c.b[i]; }
-}
-
-void pack_host(const Plan& P, const PackItem& it, const float* fold, char* dst)
-{
-    const float* sc = it.fold < 0 ? nullptr : fold + P.fold_at({ it.fold, 0 });
-    if (it.kind == PK_F32) return pack_layer_f32(reinterpret_cast<float*>(dst), it.w, sc, it.Co, it.Ci, it.taps, it.CoP, it.CiP);
-    uint16_t* o = reinterpret_cast<uint16_t*>(dst);
-    if (it.kind == PK_BLOCKS) {
-        if (it.CBC == 64) pack_layer_generic(o, P.dtype, it.w, sc, it.Co, it.Ci, it.taps, it.CoP, it.CiP);
-        else pack_layer_wide128(o, P.dtype, it.w, sc, it.Co, it.Ci, it.taps, it.CoP, it.CiP, it.CBC);
-        return;
+    auto at = [&](FoldRef r) { return fold + P.fold_at(r); };
+    for (size_t i = 0; i < P.folds.size(); ++i) { P.folds[i].scale = at({ (int)i, 0 }); P.folds[i].shift = at({ (int)i, 1 }); }
+    for (PackJob& j : P.packs) {
+        j.scale = j.fold < 0 ? nullptr : at({ j.fold, 0 });
+        j.dst = base[j.buf] + j.off;
+        j.block0 = P.pack_blocks;
+        P.pack_blocks += (j.groups + PACK_THREADS - 1) / PACK_THREADS;
     }
-    constexpr size_t FRAG = 512;
-    std::vector<uint16_t> f;                     // the layer's own fragments; the item's padding stays zero
-    pack_layer(f, P.dtype, it.w, sc, it.Co, it.Ci, it.taps, it.KS, it.MS, it.ci0, it.centre_first != 0, it.perm);
-    if (it.chunk_frags == 8) { memcpy(o, f.data(), f.size() * 2); return; }
-    for (size_t c = 0; c * it.chunk_frags * FRAG < f.size(); ++c)
-        memcpy(o + c * 8 * FRAG, f.data() + c * it.chunk_frags * FRAG, it.chunk_frags * FRAG * 2);
-}
-
-void copy_host(const Plan& P, const CopyItem& it, const float* fold, float* dst)
-{
-    const float* src = it.fsrc.item < 0 ? it.src : fold + P.fold_at(it.fsrc);
-    if (it.kind == CP_COPY) memcpy(dst, src, sizeof(float) * it.n);
-    else if (it.kind == CP_MULS) {
-        const float s = fold[P.fold_at({ it.scale_of, 0 })];
-        for (int i = 0; i < it.n; ++i) dst[i] = src[i] * s;
-    } else if (it.kind == CP_FC4) {
-        for (int j = 0; j < KH_VALUE_WIDTH; ++j)
-            for (int k = 0; k < 64; ++k) dst[((size_t)(k / 4) * KH_VALUE_WIDTH + j) * 4 + (k & 3)] = src[(size_t)j * 64 + k];
-    } else {
-        for (int co = 0; co < it.Co; ++co)
-            for (int ci = 0; ci < it.Ci; ++ci)
-                for (int k = 0; k < it.taps; ++k)
-                    dst[((size_t)k * it.Ci + ci) * it.Co + co] = src[((size_t)co * it.Ci + ci) * it.taps + k];
+    for (CopyJob& j : P.copies) {
+        if (j.fsrc.item >= 0) j.src = at(j.fsrc);
+        j.s = j.scale_of < 0 ? nullptr : at({ j.scale_of, 0 });
+        j.dst = reinterpret_cast<float*>(base[j.buf]) + j.off;
+        j.block0 = P.copy_blocks;
+        P.copy_blocks += (j.npad + PACK_THREADS - 1) / PACK_THREADS;
     }
 }
 
-int run_host(Weights& W, const Plan& P)
+// one pack job on the host: a fragment decoded once, its 64 lanes emitted  (the job by value: no store aliases it)
+void pack_job_host(const PackJob jb)
+{
+    for (unsigned frag = 0; frag < jb.groups / 64; ++frag) {
+        const PackFrag f = pack_decode(jb, frag);
+        if (jb.kind == PK_F32)
+            for (int l = 0; l < 64; ++l) static_cast<float4*>(jb.dst)[frag * 64 + l] = pack_emit32(jb, f, l);
+        else
+            for (int l = 0; l < 64; ++l) static_cast<uint4*>(jb.dst)[frag * 64 + l] = pack_emit16(jb, f, l);
+    }
+}
+
+// one copy job: a row decoded once, its elements emitted
+void copy_job_host(const CopyJob jb)
+{
+    const unsigned len = copy_row_len(jb);
+    for (unsigned i0 = 0; i0 < jb.npad; i0 += len) {
+        const float* row = copy_decode(jb, i0 / len);
+        for (unsigned x = 0; x < len; ++x) jb.dst[i0 + x] = copy_emit(jb, row, i0, x);
+    }
+}
+
+int run_host(Weights& W, Plan& P)
 {
     std::vector<float> fold(P.fold_floats());
-    for (size_t i = 0; i < P.folds.size(); ++i) fold_item(P.folds[i], fold.data() + P.fold_at({ (int)i, 0 }), fold.data() + P.fold_at({ (int)i, 1 }));
     std::vector<char> host[NBUF];
-    for (int b = 0; b < NBUF; ++b) host[b].assign(P.bytes[b], 0);
+    char* base[NBUF];
+    for (int b = 0; b < NBUF; ++b) { host[b].assign(P.bytes[b], 0); base[b] = host[b].data(); }
+    bind(P, fold.data(), base);
+    for (const FoldJob& j : P.folds)
+        for (int i = 0; i < j.co; ++i) fold_channel(j, i);
     {
         // the jobs run on a few host threads (a 20x256 net is 48 M fragments' worth)
         std::atomic<size_t> next{ 0 };
         auto run = [&]() {
-            for (size_t j; (j = next.fetch_add(1)) < P.packs.size();) pack_host(P, P.packs[j], fold.data(), host[P.packs[j].buf].data() + P.packs[j].off);
+            for (size_t j; (j = next.fetch_add(1)) < P.packs.size();) pack_job_host(P.packs[j]);
         };
         const int nt = P.threads ? (int)std::min<size_t>(8, P.packs.size()) : 1;
         std::vector<std::thread> th;
@@ -465,7 +365,7 @@ int run_host(Weights& W, const Plan& P)
         run();
         for (auto& t : th) t.join();
     }
-    for (const CopyItem& it : P.copies) copy_host(P, it, fold.data(), reinterpret_cast<float*>(host[it.buf].data()) + it.off);
+    for (const CopyJob& j : P.copies) copy_job_host(j);
     int rc = alloc_buffers(W, P);
     if (rc) return rc;
     for (int b = 0; b < NBUF; ++b)
@@ -473,56 +373,28 @@ int run_host(Weights& W, const Plan& P)
     return KH_OK;
 }
 
-// ------------------------------------------------------------------------------- the device packer
-// The plan as job tables in device memory and three launches on `st` (fold, pack, copy).  `scratch` (the folded arrays
-// and the tables) and `tables` (their host source) must live until the stream has run them.
-int run_device(Weights& W, const Plan& P, hipStream_t st, DevMem& scratch, std::vector<char>& tables)
+// The jobs as tables in device memory and three launches on `st` (fold, pack, copy).  `scratch` (the folded arrays and
+// the tables) and `tables` (their host source) must live until the stream has run them.
+int run_device(Weights& W, Plan& P, hipStream_t st, DevMem& scratch, std::vector<char>& tables)
 {
     int rc = alloc_buffers(W, P);
     if (rc) return rc;
     const size_t fold_bytes = (P.fold_floats() * 4 + 15) / 16 * 16;
-    const size_t nf = P.folds.size(), np = P.packs.size(), nc = P.copies.size();
-    const size_t at_f = 0, at_p = (at_f + nf * sizeof(FoldJob) + 15) / 16 * 16, at_c = (at_p + np * sizeof(PackJob) + 15) / 16 * 16;
-    tables.assign(at_c + nc * sizeof(CopyJob), 0);
-    if (scratch.ensure(fold_bytes + tables.size())) return KH_ERR_HIP;
-    float* d_fold = scratch.as<float>();
+    const size_t nf = P.folds.size() * sizeof(FoldJob), np = P.packs.size() * sizeof(PackJob), nc = P.copies.size() * sizeof(CopyJob);
+    const size_t at_f = 0, at_p = (at_f + nf + 15) / 16 * 16, at_c = (at_p + np + 15) / 16 * 16;
+    if (scratch.ensure(fold_bytes + at_c + nc)) return KH_ERR_HIP;
+    char* base[NBUF];
+    for (int b = 0; b < NBUF; ++b) base[b] = buf_of(W, b).as<char>();
+    bind(P, scratch.as<float>(), base);
+    tables.assign(at_c + nc, 0);
+    memcpy(tables.data() + at_f, P.folds.data(), nf);
+    memcpy(tables.data() + at_p, P.packs.data(), np);
+    memcpy(tables.data() + at_c, P.copies.data(), nc);
     char* d_tab = scratch.as<char>() + fold_bytes;
-    FoldJob* fj = reinterpret_cast<FoldJob*>(tables.data() + at_f);
-    PackJob* pj = reinterpret_cast<PackJob*>(tables.data() + at_p);
-    CopyJob* cj = reinterpret_cast<CopyJob*>(tables.data() + at_c);
-    for (size_t i = 0; i < nf; ++i) {
-        const ConvBN& c = P.folds[i].c;
-        fj[i] = { c.b, c.g, c.be, c.rm, c.rv, d_fold + P.fold_at({ (int)i, 0 }), d_fold + P.fold_at({ (int)i, 1 }), P.folds[i].co };
-    }
-    unsigned pblocks = 0, cblocks = 0;
-    for (size_t i = 0; i < np; ++i) {
-        const PackItem& it = P.packs[i];
-        PackJob& j = pj[i];
-        j.w = it.w;
-        j.scale = it.fold < 0 ? nullptr : d_fold + P.fold_at({ it.fold, 0 });
-        j.dst = buf_of(W, it.buf).as<char>() + it.off;
-        j.groups = (unsigned)(it.bytes / 16);
-        j.block0 = pblocks;
-        j.kind = it.kind; j.dtype = P.dtype; j.Co = it.Co; j.Ci = it.Ci; j.taps = it.taps;
-        j.KS = it.KS; j.MS = it.MS; j.ci0 = it.ci0; j.centre_first = it.centre_first; j.perm = it.perm; j.chunk_frags = it.chunk_frags;
-        j.CiP = it.CiP; j.CBC = it.CBC;
-        pblocks += (j.groups + PACK_THREADS - 1) / PACK_THREADS;
-    }
-    for (size_t i = 0; i < nc; ++i) {
-        const CopyItem& it = P.copies[i];
-        CopyJob& j = cj[i];
-        j.src = it.fsrc.item < 0 ? it.src : d_fold + P.fold_at(it.fsrc);
-        j.s = it.scale_of < 0 ? nullptr : d_fold + P.fold_at({ it.scale_of, 0 });
-        j.dst = buf_of(W, it.buf).as<float>() + it.off;
-        j.n = (unsigned)it.n; j.npad = (unsigned)it.npad;
-        j.block0 = cblocks;
-        j.kind = it.kind; j.Co = it.Co; j.Ci = it.Ci; j.taps = it.taps;
-        cblocks += (j.npad + PACK_THREADS - 1) / PACK_THREADS;
-    }
     HIPCHK(hipMemcpyAsync(d_tab, tables.data(), tables.size(), hipMemcpyHostToDevice, st));
-    HIPCHK(launch_fold(reinterpret_cast<const FoldJob*>(d_tab + at_f), (int)nf, st));
-    HIPCHK(launch_pack(reinterpret_cast<const PackJob*>(d_tab + at_p), (int)np, pblocks, st));
-    HIPCHK(launch_copy(reinterpret_cast<const CopyJob*>(d_tab + at_c), (int)nc, cblocks, st));
+    HIPCHK(launch_fold(reinterpret_cast<const FoldJob*>(d_tab + at_f), (int)P.folds.size(), st));
+    HIPCHK(launch_pack(reinterpret_cast<const PackJob*>(d_tab + at_p), (int)P.packs.size(), P.pack_blocks, st));
+    HIPCHK(launch_copy(reinterpret_cast<const CopyJob*>(d_tab + at_c), (int)P.copies.size(), P.copy_blocks, st));
     return KH_OK;
 }
 
@@ -538,13 +410,11 @@ void install(kh_engine* e, const std::shared_ptr<Weights>& W, std::shared_ptr<We
 void set_vshift(Weights& W, const HostNet& host)
 {
     float vs;
-    fold_bn(host.vconv, 1, &vs, &W.ly_vshift);
+    fold_channel(fold_job(host.vconv, 1, &vs, &W.ly_vshift), 0);
 }
 
-}  // namespace
-
-int load_weights_impl(kh_engine* e, const float* blob, size_t nfloats, int generation, int64_t bn_batches,
-                      std::shared_ptr<Weights>* installed)
+// what both ways of installing begin with: the blob's size checked, the engine's device current, a new set
+int begin_install(kh_engine* e, const float* blob, size_t nfloats, int generation, int64_t bn_batches, std::shared_ptr<Weights>& W)
 {
     if (!e || !blob) return fail(KH_ERR_INVALID, "null argument");
     const int F = e->cfg.features, C = e->cfg.filters, R = e->cfg.residuals;
@@ -553,9 +423,21 @@ int load_weights_impl(kh_engine* e, const float* blob, size_t nfloats, int gener
                     nfloats, kh_weight_count(F, C, R), F, C, R);
     int rc = set_device(e);
     if (rc) return rc;
-    auto W = std::make_shared<Weights>();
+    W = std::make_shared<Weights>();
     W->generation = generation;
     W->bn_batches = bn_batches;
+    return KH_OK;
+}
+
+}  // namespace
+
+int load_weights_impl(kh_engine* e, const float* blob, size_t nfloats, int generation, int64_t bn_batches,
+                      std::shared_ptr<Weights>* installed)
+{
+    std::shared_ptr<Weights> W;
+    int rc = begin_install(e, blob, nfloats, generation, bn_batches, W);
+    if (rc) return rc;
+    const int F = e->cfg.features, C = e->cfg.filters, R = e->cfg.residuals;
     W->blob.assign(blob, blob + nfloats);
     const HostNet n = parse_blob(W->blob.data(), F, C, R);
     Plan P;
@@ -568,13 +450,10 @@ int load_weights_impl(kh_engine* e, const float* blob, size_t nfloats, int gener
 int load_weights_device_impl(kh_engine* e, const float* d_blob, size_t nfloats, int generation, int64_t bn_batches,
                              hipStream_t stream, PinMem* pin, std::shared_ptr<Weights>* installed)
 {
-    if (!e || !d_blob) return fail(KH_ERR_INVALID, "null argument");
-    const int F = e->cfg.features, C = e->cfg.filters, R = e->cfg.residuals;
-    if (nfloats != kh_weight_count(F, C, R))
-        return fail(KH_ERR_INVALID, "weight blob has %zu floats, expected %zu for F=%d C=%d R=%d",
-                    nfloats, kh_weight_count(F, C, R), F, C, R);
-    int rc = set_device(e);
+    std::shared_ptr<Weights> W;
+    int rc = begin_install(e, d_blob, nfloats, generation, bn_batches, W);
     if (rc) return rc;
+    const int F = e->cfg.features, C = e->cfg.filters, R = e->cfg.residuals;
     {
         hipPointerAttribute_t at;
         if (hipPointerGetAttributes(&at, d_blob) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != e->cfg.device) {
@@ -599,9 +478,6 @@ int load_weights_device_impl(kh_engine* e, const float* d_blob, size_t nfloats, 
     HIPCHK(hipEventRecord(e->ld_ready, st));
     HIPCHK(hipStreamWaitEvent(e->ld_copy, e->ld_ready, 0));
     HIPCHK(hipMemcpyAsync(pin->p, d_blob, nfloats * 4, hipMemcpyDeviceToHost, e->ld_copy));
-    auto W = std::make_shared<Weights>();
-    W->generation = generation;
-    W->bn_batches = bn_batches;
     Plan P;
     DevMem scratch;
     std::vector<char> tables;

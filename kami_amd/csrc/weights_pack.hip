@@ -1,9 +1,8 @@
-// weights_pack.hip — the device packer: HIP kernels that read the canonical fp32 blob from device memory and write a
-// parameter set's serving buffers, bit for bit what the host loops of weights.hip write (fold_bn, pack_layer,
-// pack_layer_generic, pack_layer_wide128, pack_layer_f32, the [tap][ci][co] transpose, the fc4 re-lay).  Every layout
-// is an index map from an output element to (co, ci, tap), one multiply by the channel's scale and one rounding, so a
-// thread produces one 16-byte group and stores it whole; padding (rows >= Co, channels >= Ci, empty fragments, the
-// parity chunk) is written as zeros, never assumed.
+// weights_pack.hip — the device packer: three kernels that run a parameter set's jobs (weights_pack.h) on a canonical
+// fp32 blob in device memory.  The layouts, the fold and the roundings are weights_pack.h's functions, the ones the host
+// packer loops over; here a thread folds one channel, or decodes its fragment and stores its lane's 16-byte group whole,
+// or writes one float.  Padding (rows >= Co, channels >= Ci, empty fragments, the parity chunk) is written as zeros,
+// never assumed.
 //
 // This file is compiled with -ffp-contract=off (kami_amd/build.py): the host folds BatchNorm with a subtract, a
 // multiply and an add, and a fused multiply-add here would change the last bit of a shift.  `/` and sqrtf are
@@ -16,14 +15,7 @@ namespace {
 __global__ void __launch_bounds__(PACK_THREADS) fold_kernel(const FoldJob* __restrict__ jobs)
 {
     const FoldJob jb = jobs[blockIdx.x];
-    for (int i = threadIdx.x; i < jb.co; i += PACK_THREADS) {
-        if (!jb.g) { jb.scale[i] = 1.0f; jb.shift[i] = jb.b[i]; continue; }
-        const float s = jb.g[i] / sqrtf(jb.rv[i] + 1e-5f);
-        const float d = jb.b[i] - jb.rm[i];
-        const float p = d * s;
-        jb.scale[i] = s;
-        jb.shift[i] = p + jb.be[i];
-    }
+    for (int i = threadIdx.x; i < jb.co; i += PACK_THREADS) fold_channel(jb, i);
 }
 
 // the job whose block range holds `block`: jobs are sorted by block0
@@ -37,72 +29,14 @@ template <class J> __device__ inline int find_job(const J* jobs, int njobs, unsi
     return lo;
 }
 
-__device__ inline float element(const PackJob& jb, int co, int ci, int tap)
-{
-    if (co >= jb.Co || ci >= jb.Ci) return 0.0f;
-    return jb.w[((size_t)co * jb.Ci + ci) * jb.taps + tap] * (jb.scale ? jb.scale[co] : 1.0f);
-}
-
 __global__ void __launch_bounds__(PACK_THREADS) pack_kernel(const PackJob* __restrict__ jobs, int njobs)
 {
     const PackJob& jb = jobs[find_job(jobs, njobs, blockIdx.x)];
     const unsigned g = (blockIdx.x - jb.block0) * PACK_THREADS + threadIdx.x;
     if (g >= jb.groups) return;
-    const int l = g & 63, r = l & 31, h = l >> 5;
-    if (jb.kind == PK_F32) {
-        const unsigned per_cb = (unsigned)jb.taps * (jb.CiP / 8) * 128, full = (unsigned)jb.taps * 16 * 128;
-        const int cb = g / per_cb;
-        unsigned t = g % per_cb;
-        const int slice = t / full;
-        t -= slice * full;
-        const int len8 = (jb.CiP - 128 * slice < 128 ? jb.CiP - 128 * slice : 128) / 8;
-        const int tap = t / (len8 * 128);
-        t %= len8 * 128;
-        const int j = slice * 16 + (t >> 7), ms = (t >> 6) & 1;
-        const int co = cb * 64 + ms * 32 + r;
-        float4 v;
-        v.x = element(jb, co, j * 8 + 4 * h + 0, tap);
-        v.y = element(jb, co, j * 8 + 4 * h + 1, tap);
-        v.z = element(jb, co, j * 8 + 4 * h + 2, tap);
-        v.w = element(jb, co, j * 8 + 4 * h + 3, tap);
-        static_cast<float4*>(jb.dst)[g] = v;
-        return;
-    }
-    int co = 0, tap = 0, ks = 0;
-    bool live = true, permuted = false;
-    if (jb.kind == PK_STREAM) {
-        const unsigned frag = g >> 6, chunk = frag >> 3, fi = frag & 7;
-        const unsigned sf = chunk * jb.chunk_frags + fi;
-        live = (int)fi < jb.chunk_frags && sf < (unsigned)(jb.taps * jb.KS * jb.MS);
-        const int ti = sf / (jb.KS * jb.MS), ms = sf % jb.MS;
-        ks = (sf / jb.MS) % jb.KS;
-        tap = !jb.centre_first ? ti : (ti == 0 ? 4 : (ti <= 4 ? ti - 1 : ti));
-        permuted = ti * jb.KS + ks < jb.perm;
-        co = ms * 32 + r;
-    } else {
-        const int M = jb.CBC / 32, slices = jb.CiP / 64;
-        unsigned t = g >> 6;
-        const int ms = t % M; t /= M;
-        const int kk = t & 3; t >>= 2;
-        tap = t % jb.taps; t /= jb.taps;
-        const int slice = t % slices, cb = t / slices;
-        ks = slice * 4 + kk;
-        co = cb * jb.CBC + ms * 32 + r;
-    }
-    uint16_t o[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int ci = jb.kind == PK_STREAM ? jb.ci0 + (permuted ? 32 * (ks >> 1) + 8 * (2 * (ks & 1) + (j >> 2)) + 4 * h + (j & 3) : ks * 16 + 8 * h + j)
-                                            : ks * 16 + 8 * h + j;
-        const float v = live ? element(jb, co, ci, tap) : 0.0f;
-        o[j] = jb.dtype == KH_BF16 ? f2bf16(v) : f2f16(v);
-    }
-    uint4 q;
-    q.x = o[0] | (uint32_t)o[1] << 16;
-    q.y = o[2] | (uint32_t)o[3] << 16;
-    q.z = o[4] | (uint32_t)o[5] << 16;
-    q.w = o[6] | (uint32_t)o[7] << 16;
-    static_cast<uint4*>(jb.dst)[g] = q;
+    const PackFrag f = pack_decode(jb, g >> 6);
+    if (jb.kind == PK_F32) static_cast<float4*>(jb.dst)[g] = pack_emit32(jb, f, g & 63);
+    else static_cast<uint4*>(jb.dst)[g] = pack_emit16(jb, f, g & 63);
 }
 
 __global__ void __launch_bounds__(PACK_THREADS) copy_kernel(const CopyJob* __restrict__ jobs, int njobs)
@@ -110,19 +44,8 @@ __global__ void __launch_bounds__(PACK_THREADS) copy_kernel(const CopyJob* __res
     const CopyJob& jb = jobs[find_job(jobs, njobs, blockIdx.x)];
     const unsigned i = (blockIdx.x - jb.block0) * PACK_THREADS + threadIdx.x;
     if (i >= jb.npad) return;
-    float v = 0.0f;
-    if (i < jb.n) {
-        if (jb.kind == CP_COPY) v = jb.src[i];
-        else if (jb.kind == CP_MULS) v = jb.src[i] * jb.s[0];
-        else if (jb.kind == CP_FC4) {                   // [j][k] -> [k / 4][j][4]
-            const unsigned k = (i / (4 * KH_VALUE_WIDTH)) * 4 + (i & 3), j = (i >> 2) % KH_VALUE_WIDTH;
-            v = jb.src[(size_t)j * 64 + k];
-        } else {                                        // [co][ci][tap] -> [tap][ci][co]
-            const unsigned co = i % jb.Co, ci = (i / jb.Co) % jb.Ci, k = i / ((unsigned)jb.Co * jb.Ci);
-            v = jb.src[((size_t)co * jb.Ci + ci) * jb.taps + k];
-        }
-    }
-    jb.dst[i] = v;
+    const unsigned len = copy_row_len(jb), row = i / len;
+    jb.dst[i] = copy_emit(jb, copy_decode(jb, row), row * len, i - row * len);
 }
 
 }  // namespace

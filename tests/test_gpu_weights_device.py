@@ -13,7 +13,8 @@ kernel by batch size):
                              (batch 300), the per-layer kernels on ly_w / ly_shift (batch 40)
     test_wide_256            ly_w2b (CBC 256) through tower2s_kernel (batch 64) and tower2b<256> (batch 300)
     test_generic_layout      ly_w with padded Co / Ci (C=96), ly_shift, per-layer heads (F=30: no ly_w2b)
-    test_f32                 pack_layer_f32's ly_w, ly_shift, ly_misc; `simple` (scale, shift, the [tap][ci][co] transpose)
+    test_ragged_wide_stem    a stem with CiP = 256 of which 200 channels are live (F=200: beyond the whole-network kernel)
+    test_f32                 the fp32 fragments' (PK_F32) ly_w, ly_shift, ly_misc; `simple` (scale, shift, the [tap][ci][co] transpose)
                              in a child process with KAMI_F32_SIMPLE=1
 """
 import ctypes as C
@@ -56,6 +57,10 @@ def test_wide_256():
 @pytest.mark.parametrize("filters", [96, 128])
 def test_generic_layout(filters):
     assert host_and_device_agree("bf16", 30, filters, 2, [40], blobs_for(30, filters, 2, 7)) == []
+
+
+def test_ragged_wide_stem():
+    assert host_and_device_agree("bf16", 200, 64, 1, [3], blobs_for(200, 64, 1, 21)) == []
 
 
 @pytest.mark.parametrize("filters", [64, 128])
