@@ -169,6 +169,16 @@ int  kh_train(kh_engine* e, const float* inputs, const float* obs_p, const float
  * them are the batches, a short last batch keeps the previous batch's rows behind its own (the reference's staging buffers
  * persist).  No engine needed: what a restatement of a multi-batch run has to follow. */
 int  kh_train_order(int trajectories, int epochs, int32_t* order);
+/* Which kernels one training step at `batch` boards runs for a convolution with ci input and co output channels on the
+ * matrix-core path, answered by the launchers' own functions, without an engine or a GPU (every output nullable):
+ *   *two_board_kernel  1: the convolution (forward, or a data gradient with ci and co swapped) runs conv_f32_kernel, two
+ *                      boards x 64 channels per workgroup; 0: conv_f32_small_kernel, one board x 32 channels — taken
+ *                      while ceil(batch / 2) * ceil(co / 64) < 128
+ *   *wgrad_ranges      board ranges the weight gradient is cut into (one workgroup per 64 x 64 channel tile and range,
+ *                      the ranges' partial sums added in range order)
+ *   *boards_per_range  boards of every range but the last = ceil(batch / ranges); the last holds the rest
+ * For the stem pass ci = the network's feature planes (the planes' padding to 8 does not change the answer). */
+int  kh_train_conv_plan(int batch, int ci, int co, int* two_board_kernel, int* wgrad_ranges, int* boards_per_range);
 
 /* ---- compact replay records as the trainer's input ------------------------------------------------------------
  * One finished-game position as self-play produces it (selfplay.cpp:176-184, MCTS::snapshot mcts.h:341-348): the board

@@ -68,6 +68,7 @@ SYMBOLS = {
     "kh_train_config_check": (C.c_int, [C.POINTER(TrainConfig)]),
     "kh_train_grad_norms": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
     "kh_train_order": (C.c_int, [C.c_int, C.c_int, _P]),
+    "kh_train_conv_plan": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "kh_records_validate": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "kh_expand_records": (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
     "kh_train_records": (C.c_int, [_P, _P, C.c_int, C.POINTER(TrainConfig), C.POINTER(C.c_float), C.POINTER(C.c_float)]),

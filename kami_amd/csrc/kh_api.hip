@@ -824,6 +824,16 @@ int kh_train_order(int trajectories, int epochs, int32_t* order)
     return KH_OK;
 }
 
+int kh_train_conv_plan(int batch, int ci, int co, int* two_board_kernel, int* wgrad_ranges, int* boards_per_range)
+{
+    if (batch < 1 || ci < 1 || co < 1) return fail(KH_ERR_INVALID, "kh_train_conv_plan: batch, ci and co >= 1 required");
+    const int ranges = kh::train_wgrad_splits(batch, ci, co);
+    if (two_board_kernel) *two_board_kernel = kh::conv_f32_raw_two_board(batch, co) ? 1 : 0;
+    if (wgrad_ranges) *wgrad_ranges = ranges;
+    if (boards_per_range) *boards_per_range = (batch + ranges - 1) / ranges;
+    return KH_OK;
+}
+
 int kh_checkpoint_read(const char* path, int* features, int* filters, int* residuals, int* generation,
                        float* blob, size_t cap, size_t* nfloats)
 {

@@ -119,6 +119,9 @@ constexpr size_t layers_xchg_bytes(int pairs) { return layers_xflag_bytes(pairs)
 // or out += conv(in) when `accumulate`.  packed_w: fragments in conv_f32_kernel's order, Co rounded up to 64,
 // [Co/64][Ci slices of <= 128][taps][slice/8][2][64 lanes][4] (train.hip packs them on the device).  Ci % 8 == 0.
 hipError_t conv_f32_raw_prepare();
+// which kernel launch_conv_f32_raw takes: true = conv_f32_kernel (two boards x 64 channels per workgroup), false =
+// conv_f32_small_kernel (one board x 32 channels, the reduction split over the waves)
+bool conv_f32_raw_two_board(int B, int Co);
 hipError_t launch_conv_f32_raw(const float* in, const float* packed_w, const float* bias, float* out, int B, int Ci, int Co, int taps,
                                bool accumulate, hipStream_t s);
 hipError_t launch_layers(int dtype, const LayersArgs& L, hipStream_t s);
@@ -130,6 +133,9 @@ struct StepBuffers { float* params; float* grads; float* work; };
 TrainNet* train_layout_new(int F, int C, int R);
 void train_layout_free(TrainNet* n);
 size_t train_workspace_floats(int F, int C, int R, int B);
+// board ranges of one layer's weight gradient (conv_wgrad_mfma_kernel's grid.z); every range but the last holds
+// ceil(B / ranges) boards
+int train_wgrad_splits(int B, int Ci, int Co);
 hipError_t train_step(const TrainNet& n, const StepBuffers& sb, const float* x_in, const float* obsp, const float* obsv,
                       int B, float lr, float* loss_rows /* [2 B] floats + 2 ints (NaN flags of the forward's outputs) */, hipStream_t s);
 

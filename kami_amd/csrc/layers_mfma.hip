@@ -2090,7 +2090,7 @@ template <int TAPS, int EPI> static hipError_t launch_conv_f32(const ConvArgsF32
     if (const hipError_t e = allow_lds<&conv_f32_kernel<TAPS, EPI>>(); e != hipSuccess) return e;
     // few boards (the trainer): one board x 32 channels per workgroup, the reduction split over its waves
     if constexpr (EPI == 3 || EPI == 4) {
-        if ((long)((a.B + 1) / 2) * ((a.Co + 63) / 64) < 128) {
+        if (!conv_f32_raw_two_board(a.B, a.Co)) {
             if (const hipError_t e = allow_lds<&conv_f32_small_kernel<TAPS, EPI>>(); e != hipSuccess) return e;
             const int lds1 = std::max(lds / 2, 2 * 64 * 16 * 4);
             hipLaunchKernelGGL((conv_f32_small_kernel<TAPS, EPI>), dim3(a.B, (a.Co + 31) / 32), dim3(256), lds1, s, a);
@@ -2369,6 +2369,10 @@ hipError_t conv_f32_raw_prepare()
 }
 
 // the exact-fp32 MFMA convolution for the trainer (train.hip): out = conv(in) (+ bias), raw or added to `out`
+// the raw epilogues' kernel choice (EPI 3 / 4, the trainer): with fewer than 128 two-board workgroups the small kernel
+// (one board x 32 channels per workgroup) fills the chip better.  launch_conv_f32 and kh_train_conv_plan both ask here.
+bool conv_f32_raw_two_board(int B, int Co) { return (long)((B + 1) / 2) * ((Co + 63) / 64) >= 128; }
+
 hipError_t launch_conv_f32_raw(const float* in, const float* packed_w, const float* bias, float* out, int B, int Ci, int Co, int taps,
                                bool accumulate, hipStream_t s)
 {

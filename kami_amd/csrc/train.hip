@@ -112,7 +112,9 @@ void launch_conv_tiled(const float* w, const float* bias, const float* in, float
 // One workgroup = WG_T x WG_T (co, ci) pairs — 16 x 16 on 256 threads, or 8 x 8 on ONE WAVE when that is what it
 // takes to get 64 workgroups (64 x 64 channels); the sums over the batch stay inside one thread, in a fixed
 // order.  Thread = one pair with its T taps in registers; per board the tile's dy channels and (zero-haloed)
-// x channels go through LDS.  Sums run b-major, pixel-ascending.
+// x channels go through LDS.  Sums in two levels: a board's 64 pixels ascending, then the boards' sums ascending — one
+// chain over all B * 64 terms drifts with its length (policyconv2.weight at batch 257: 9e-6 of the gradient's scale from
+// float64, nine times plain fp32 PyTorch's error; in two levels 6e-7).
 template <int T, int WG_T>
 __global__ __launch_bounds__(WG_T * WG_T) void conv_wgrad_tiled_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                               float* __restrict__ dw, float* __restrict__ db, int B, int Ci, int Co)
@@ -137,13 +139,19 @@ __global__ __launch_bounds__(WG_T * WG_T) void conv_wgrad_tiled_kernel(const flo
             x_s[pix * S + c] = ci0 + c < Ci ? x[((long)b * 64 + q) * Ci + ci0 + c] : 0.0f;
         }
         __syncthreads();
+        float bsum[T], bb = 0.0f;                                            // this board's sums
+#pragma unroll
+        for (int t = 0; t < T; ++t) bsum[t] = 0.0f;
         for (int q = 0; q < 64; ++q) {
             const float g = dy_s[q * S + col];
-            bacc += g;
+            bb += g;
             const float* xq = x_s + (T == 9 ? ((q >> 3) * 10 + (q & 7)) : q) * S + cil;     // tap (0,0) of the 3x3 window: halo offset folded in
 #pragma unroll
-            for (int t = 0; t < T; ++t) acc[t] = fmaf(g, xq[(T == 9 ? (t / 3) * 10 + t % 3 : 0) * S], acc[t]);
+            for (int t = 0; t < T; ++t) bsum[t] = fmaf(g, xq[(T == 9 ? (t / 3) * 10 + t % 3 : 0) * S], bsum[t]);
         }
+#pragma unroll
+        for (int t = 0; t < T; ++t) acc[t] += bsum[t];
+        bacc += bb;
     }
     const int co = co0 + col, ci = ci0 + cil;
     if (co < Co && ci < Ci) {
@@ -691,7 +699,7 @@ static TrainNet layout(int F, int C, int R)
 // work = train_workspace_floats() floats of activations, conv outputs, statistics and gradients).
 
 // board ranges of the weight gradient: enough workgroups to fill the chip, at least one board each
-static int train_wgrad_splits(int B, int Ci, int Co)
+int train_wgrad_splits(int B, int Ci, int Co)
 {
     const int tiles = ((Co + 63) / 64) * ((Ci + 63) / 64);
     int want = (256 + tiles - 1) / tiles;

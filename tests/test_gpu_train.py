@@ -100,7 +100,9 @@ def test_train_step_on_the_matrix_cores_vs_float64(F, C, R, B, monkeypatch):
     three; and one step of some seeds is already 1e-5 off on BOTH paths where a BatchNorm channel's batch variance is
     tiny, so the seeds here are fixed ones) against a float64 restatement of the step, every parameter tensor: both
     paths within 2e-6 of the tensor's scale (observed 6e-8) — at 64 / 128 / 256 filters (one and two staged slices of the reduction), 119
-    planes (padded to 120), batch 64 (the two-board kernel) and 24 filters (a ragged 32-channel tile)."""
+    planes (padded to 120), batch 64 and 24 filters (a ragged 32-channel tile).  Every shape here takes conv_f32_small_kernel
+    and one board per weight-gradient range (tests/test_train_large_batch_data.py asks kh_train_conv_plan); the two-board
+    kernel, longer board ranges and the gradient's own scale are tests/test_gpu_train_large_batch.py's."""
     rng = np.random.default_rng(0)
     blob = W.random_weights(F, C, R, seed=4, peaky=3.0)
     x = rng.random((B, 8, 8, F), dtype=np.float32)

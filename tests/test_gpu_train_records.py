@@ -93,7 +93,9 @@ def test_expand_is_exact():
 CASES = [(16, 1, 11, 4, 2),        # ragged last batch at a small width
          (64, 2, 307, 8, 2),       # the reference's defaults: ring 512 x 60 %, batch 8: ragged last batch
          (64, 1, 5, 8, 1),         # the first batch is shorter than the batch size
-         (256, 1, 40, 8, 2)]       # 256 filters: the matrix-core convolutions with channel slices
+         (256, 1, 40, 8, 2),       # 256 filters: the matrix-core convolutions with channel slices
+         (64, 1, 257, 257, 1)]     # one batch of 257: the record expansion feeds the large-batch step (two-board convolutions,
+                                   # weight-gradient ranges of two boards, an odd batch)
 
 
 @pytest.mark.gpu
