@@ -216,6 +216,52 @@ int  kh_expand_records(kh_engine* e, const kh_record* rec, int n,
 int  kh_train_records(kh_engine* e, const kh_record* rec, int n,
                       const kh_train_config* cfg, float* first_loss, float* last_loss);
 
+/* ---- a replay ring of compact records in device memory ---------------------------------------------------------
+ * CompactReplayBuffer (host/replaybuffer.h; ks_ring_* in kami_search.h) with its storage on the GPU: records gathered
+ * over RCCL go in where they lie and kh_train_replay trains from the ring in place, so between self-play and the
+ * training step only a sample order crosses PCIe.  For the same capacity, seed and sequence of calls the ring holds the
+ * bytes the host ring holds and kh_replay_select returns the bytes ks_ring_select returns.
+ *   The ring lives on e's device and is independent of e afterwards: any engine on that device with features == 30
+ * may train from it, and destroying e does not invalidate it.  capacity in [1, 1 << 24] (KH_ERR_INVALID otherwise,
+ * checked before any device work).  Storage: kh_board[capacity], value[], nact[], actions[][96], visits[][96], each
+ * array 16-byte aligned, zeroed at creation and by kh_replay_clear — a never-written slot is the all-zero record, a
+ * valid sample.  head (next slot to write, from 0), the count of records ever added and the generator
+ * (std::mt19937_64(seed); one draw is rng() % capacity) live on the host under the ring's mutex: an add writes record
+ * i to slot (head + i) % capacity, then head = (head + n) % capacity and count += n; of an add with n > capacity only
+ * the last `capacity` records are written (all n are validated); clear resets head, count and the memory, not the
+ * generator.  Every entry point may be called from any thread. */
+typedef struct kh_replay kh_replay;
+int     kh_replay_create(kh_engine* e, int capacity, uint64_t seed, kh_replay** out);
+void    kh_replay_destroy(kh_replay* r);
+/* Records are validated when they are added, by kh_records_validate's rules, so every slot is a valid training sample
+ * at all times.  A failed add returns KH_ERR_INVALID, *bad_index (nullable; -1 when the records are not to blame) and the
+ * message kh_records_validate gives for the same records, and leaves the ring, head, count and the generator as they
+ * were.  kh_replay_add takes host records.
+ *   kh_replay_add_device takes n kh_record structs (664-byte stride) in device memory of the ring's device, 8-byte
+ * aligned, n of them inside one allocation — anything else is KH_ERR_INVALID, decided on the host before any device
+ * work.  A HIP kernel validates them (one wavefront per record; the first offence in record order, then entry order, as
+ * on the host) and a second one behind it moves them into the ring, on `stream` (a hipStream_t; NULL: the ring's own),
+ * ordered behind what the caller queued there.  The call returns once the records are in the ring or it has failed,
+ * after one synchronisation: the caller may free d_rec right after. */
+int     kh_replay_add(kh_replay* r, const kh_record* rec, int n, int* bad_index);
+int     kh_replay_add_device(kh_replay* r, const void* d_rec, int n, void* stream, int* bad_index);
+int64_t kh_replay_count(kh_replay* r);       /* records ever added (since the last clear); 0 for NULL */
+int     kh_replay_size(kh_replay* r);        /* capacity; 0 for NULL                                  */
+int     kh_replay_clear(kh_replay* r);
+/* Slots first_slot .. first_slot + n - 1 (mod capacity) as records in host memory, pad bytes of the board as they were
+ * given; no draw is made.  For tests, for dumping a ring and for moving one. */
+int     kh_replay_read(kh_replay* r, int first_slot, int n, kh_record* out);
+/* n draws with replacement over ALL slots (replaybuffer.h:61-84), the records of those slots in host memory. */
+int     kh_replay_select(kh_replay* r, int n, kh_record* out);
+/* Makes n draws and trains on the records in those slots, read where they lie: the same effect as kh_replay_select
+ * followed by kh_train_records(e, those, n, cfg, ...) — parameters, BatchNorm statistics, both losses, kh_generation,
+ * kh_bn_batches, kh_train_grad_norms, status and message of a failed call match bit for bit — with the sample order
+ * (epochs x n int32) as the only upload.  kh_train_records' argument checks, plus: ring and engine on one device,
+ * cfg.features == 30.  A call these checks reject makes no draw; one that fails later (a NaN loss) has made its n.
+ * Adds to the ring wait until the call returns. */
+int     kh_train_replay(kh_engine* e, kh_replay* r, int n, const kh_train_config* cfg,
+                        float* first_loss, float* last_loss);
+
 /* NN::read nn.cpp:204-222: parse a checkpoint file without an engine.  Two containers are understood:
  * the reference's own — the libtorch archive NN::write leaves (nn.cpp:189-202: module.save + the
  * "generation" IValue), read here with a zip walk and a pickle stack machine (csrc/torch_archive.h; no

@@ -72,6 +72,16 @@ SYMBOLS = {
     "kh_records_validate": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
     "kh_expand_records": (C.c_int, [_P, _P, C.c_int, _P, _P, _P]),
     "kh_train_records": (C.c_int, [_P, _P, C.c_int, C.POINTER(TrainConfig), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "kh_replay_create": (C.c_int, [_P, C.c_int, C.c_uint64, C.POINTER(_P)]),
+    "kh_replay_destroy": (None, [_P]),
+    "kh_replay_add": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
+    "kh_replay_add_device": (C.c_int, [_P, _P, C.c_int, _P, C.POINTER(C.c_int)]),
+    "kh_replay_count": (C.c_int64, [_P]),
+    "kh_replay_size": (C.c_int, [_P]),
+    "kh_replay_clear": (C.c_int, [_P]),
+    "kh_replay_read": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "kh_replay_select": (C.c_int, [_P, C.c_int, _P]),
+    "kh_train_replay": (C.c_int, [_P, _P, C.c_int, C.POINTER(TrainConfig), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "kh_checkpoint_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                      _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "kh_checkpoint_read_ex": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),

@@ -21,7 +21,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libkamihip.so")
 ARCH = "gfx950"
-SOURCES = ["kh_api.hip", "weights.hip", "weights_pack.hip", "queue.hip", "encode.hip", "forward_simple.hip", "tower_mfma.hip", "tower8_mfma.hip", "layers_mfma.hip", "train.hip", "train_ingest.hip"]
+SOURCES = ["kh_api.hip", "weights.hip", "weights_pack.hip", "queue.hip", "encode.hip", "forward_simple.hip", "tower_mfma.hip", "tower8_mfma.hip", "layers_mfma.hip", "train.hip", "train_ingest.hip", "replay_ring.hip"]
 # MFMA results in arch VGPRs: the epilogues read them with VALU ops and would otherwise pay a
 # v_accvgpr_read per value (the kernel runs one wave per SIMD, registers are not scarce).
 # weights_pack.hip: the device packer folds BatchNorm with the host packer's three roundings (subtract, multiply, add);

@@ -5,12 +5,14 @@
 // recorded training step reads (TrainCache dx / dp / dv): planes through encode_square(), so they are the encoder's
 // bits by construction; the 4 672-float visit row; the value.  The step itself — train_step, recorded as a graph — is
 // kh_train's, untouched, which is what makes kh_train_records equal to kh_train on the expanded arrays bit for bit.
+// kh_train_replay is the same call with a device replay ring (replay_ring.hip) as its record block: nothing but the
+// sample order, composed with the ring's draws, goes up.
 //
 // One wavefront per row, lane = POV square (encode_f32_kernel's structure).  The wave owns 4 672 floats of LDS, used
 // twice: as the [64][30] plane tile, then as the visit row, which is zeroed, scattered into and only then streamed
 // out, with a barrier between each two of those — the zero fill and the scatter hit the same addresses, and nothing
 // here depends on the order in which a wave's global stores land.
-#include "engine.h"
+#include "replay_ring.h"
 #include "encode_square.h"
 
 #include <algorithm>
@@ -111,6 +113,15 @@ void launch_expand_records(const char* d_block, const RecordBlock& lay, const in
                        reinterpret_cast<const float*>(d_block + lay.visits), d_order, base, count, dx, dp, dv);
 }
 
+int record_fail(int rule, int record, int value, int entry)
+{
+    switch (rule) {
+    case RECORD_BAD_NACT: return fail(KH_ERR_INVALID, "record %d: nact %d outside [0, %d]", record, value, KH_MAX_RECORD_ACTIONS);
+    case RECORD_BAD_RANGE: return fail(KH_ERR_INVALID, "record %d: action %d (entry %d) outside [0, %d)", record, value, entry, KH_PSIZE);
+    default: return fail(KH_ERR_INVALID, "record %d: action %d appears twice (entry %d); actions must be pairwise distinct", record, value, entry);
+    }
+}
+
 int records_check(const kh_record* rec, int n, int* bad_index)
 {
     if (bad_index) *bad_index = -1;
@@ -121,19 +132,19 @@ int records_check(const kh_record* rec, int n, int* bad_index)
         auto bad = [&]() { if (bad_index) *bad_index = i; };
         if (r.nact < 0 || r.nact > KH_MAX_RECORD_ACTIONS) {
             bad();
-            return fail(KH_ERR_INVALID, "record %d: nact %d outside [0, %d]", i, (int)r.nact, KH_MAX_RECORD_ACTIONS);
+            return record_fail(RECORD_BAD_NACT, i, (int)r.nact, 0);
         }
         int rc = KH_OK, k = 0;
         for (; k < r.nact; ++k) {
             const int a = r.actions[k];
             if (a < 0 || a >= KH_PSIZE) {
                 bad();
-                rc = fail(KH_ERR_INVALID, "record %d: action %d (entry %d) outside [0, %d)", i, a, k, KH_PSIZE);
+                rc = record_fail(RECORD_BAD_RANGE, i, a, k);
                 break;
             }
             if (seen[a >> 6] >> (a & 63) & 1) {
                 bad();
-                rc = fail(KH_ERR_INVALID, "record %d: action %d appears twice (entry %d); actions must be pairwise distinct", i, a, k);
+                rc = record_fail(RECORD_BAD_TWICE, i, a, k);
                 break;
             }
             seen[a >> 6] |= (uint64_t)1 << (a & 63);
@@ -149,6 +160,78 @@ constexpr int EXPAND_CHUNK = 512;        // records per pass of kh_expand_record
 }  // namespace kh
 
 using namespace kh;
+
+// A training call on records, behind its argument checks: kh_train_records on the call's own records (`rec`, uploaded in
+// RecordBlock(n) layout), kh_train_replay on n draws from a ring (`ring`, its mutex held by the caller), whose storage
+// is the record block as it lies — the draws are composed into the sample order, which is then all that goes up.
+static int train_on_records(kh_engine* e, const char* who, const kh_record* rec, kh_replay* ring, int n, const kh_train_config* cfg,
+                            float* first_loss, float* last_loss)
+{
+    int rc;
+    TrainCall call;
+    if ((rc = train_begin(e, cfg, who, call))) return rc;
+    TrainCache& tc = *call.tc;
+    hipStream_t st = call.st;
+    const int B = cfg->batch, epochs = cfg->epochs;
+    const int per_epoch = (n + B - 1) / B;
+    const size_t nsteps = (size_t)epochs * per_epoch, slot = kh::train_result_floats(B);      // floats of one step's dloss block
+
+    // records and order through one page-locked block, one copy each; the order is kh_train's (kh_train_order)
+    const RecordBlock lay(ring ? (size_t)ring->capacity : (size_t)n);
+    const size_t rec_bytes = ring ? 0 : lay.bytes, order_bytes = (size_t)epochs * n * 4;
+    if (tc.pin_rec.ensure(rec_bytes + order_bytes) || tc.rec.ensure(rec_bytes) || tc.order.ensure(order_bytes) ||
+        tc.pin_loss.ensure(nsteps * slot * 4))
+        return KH_ERR_HIP;
+    if (rec) lay.pack(tc.pin_rec.at(0), rec, (size_t)n);
+    int32_t* order = reinterpret_cast<int32_t*>(tc.pin_rec.at(rec_bytes));
+    if ((rc = kh_train_order(n, epochs, order))) return rc;
+    if (ring) {
+        // sample k of the call is the record in slot draw[k], as kh_replay_select would have returned it
+        std::vector<int32_t> draw((size_t)n);
+        for (int k = 0; k < n; ++k) draw[(size_t)k] = (int32_t)(ring->rng() % (uint64_t)ring->capacity);
+        for (size_t i = 0; i < (size_t)epochs * n; ++i) order[i] = draw[(size_t)order[i]];
+    } else
+        HIPCHK(hipMemcpyAsync(tc.rec.p, tc.pin_rec.p, lay.bytes, hipMemcpyHostToDevice, st));
+    const char* block = ring ? ring->mem.as<char>() : tc.rec.as<char>();
+    HIPCHK(hipMemcpyAsync(tc.order.p, order, order_bytes, hipMemcpyHostToDevice, st));
+    // kh_train zeroes its staging rows at the start of every call and a short batch keeps the rows behind its own:
+    // the device rows live in the cache across calls, so they start from zero here
+    HIPCHK(hipMemsetAsync(tc.dx.p, 0, (size_t)B * XR_TILE * 4, st));
+    HIPCHK(hipMemsetAsync(tc.dp.p, 0, (size_t)B * KH_PSIZE * 4, st));
+    HIPCHK(hipMemsetAsync(tc.dv.p, 0, (size_t)B * 4, st));
+    float* slots = reinterpret_cast<float*>(tc.pin_loss.p);
+    call.t_setup = std::chrono::steady_clock::now();
+    size_t step = 0;
+    for (int epoch = 0; epoch < epochs; ++epoch)
+        for (int base = 0; base < n; base += B, ++step) {
+            launch_expand_records(block, lay, tc.order.as<int32_t>() + (size_t)epoch * n, base, std::min(B, n - base),
+                                  tc.dx.as<float>(), tc.dp.as<float>(), tc.dv.as<float>(), st);
+            HIPCHK(hipGetLastError());
+            if ((rc = train_launch_step(call))) return rc;
+            HIPCHK(hipMemcpyAsync(slots + step * slot, tc.dloss.p, slot * 4, hipMemcpyDeviceToHost, st));
+        }
+    HIPCHK(hipStreamSynchronize(st));                         // the one synchronisation of the call
+    // kh_train's bookkeeping over the steps in order: the first failing step decides status and message (nothing is
+    // installed before the end of the call, so running the later steps changed nothing that is kept)
+    float firstloss = 0.0f, lastloss = 0.0f;
+    step = 0;
+    for (int epoch = 0; epoch < epochs; ++epoch) {
+        float avgloss = 0.0f;
+        for (int b = 0; b < per_epoch; ++b, ++step) {
+            float loss;
+            if ((rc = train_step_result(call, slots + step * slot, cfg->detect_anomaly != 0, epoch, b, &loss))) return rc;
+            avgloss += loss;
+        }
+        avgloss /= (float)per_epoch;
+        if (!epoch) firstloss = avgloss;
+        lastloss = avgloss;
+    }
+    call.t_steps = std::chrono::steady_clock::now();
+    if ((rc = train_finish(e, call, n, epochs))) return rc;
+    if (first_loss) *first_loss = firstloss;
+    if (last_loss) *last_loss = lastloss;
+    return KH_OK;
+}
 
 extern "C" {
 
@@ -196,62 +279,20 @@ int kh_train_records(kh_engine* e, const kh_record* rec, int n, const kh_train_c
     if (rc) return rc;
     if ((rc = kh_train_config_check(cfg))) return rc;
     if ((rc = records_check(rec, n, nullptr))) return rc;
-    TrainCall call;
-    if ((rc = train_begin(e, cfg, "kh_train_records", call))) return rc;
-    TrainCache& tc = *call.tc;
-    hipStream_t st = call.st;
-    const int B = cfg->batch, epochs = cfg->epochs;
-    const int per_epoch = (n + B - 1) / B;
-    const size_t nsteps = (size_t)epochs * per_epoch, slot = kh::train_result_floats(B);      // floats of one step's dloss block
+    return train_on_records(e, "kh_train_records", rec, nullptr, n, cfg, first_loss, last_loss);
+}
 
-    // records and order through one page-locked block, one copy each; the order is kh_train's (kh_train_order)
-    const RecordBlock lay((size_t)n);
-    const size_t order_bytes = (size_t)epochs * n * 4;
-    if (tc.pin_rec.ensure(lay.bytes + order_bytes) || tc.rec.ensure(lay.bytes) || tc.order.ensure(order_bytes) ||
-        tc.pin_loss.ensure(nsteps * slot * 4))
-        return KH_ERR_HIP;
-    lay.pack(tc.pin_rec.at(0), rec, (size_t)n);
-    int32_t* order = reinterpret_cast<int32_t*>(tc.pin_rec.at(lay.bytes));
-    if ((rc = kh_train_order(n, epochs, order))) return rc;
-    HIPCHK(hipMemcpyAsync(tc.rec.p, tc.pin_rec.p, lay.bytes, hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(tc.order.p, order, order_bytes, hipMemcpyHostToDevice, st));
-    // kh_train zeroes its staging rows at the start of every call and a short batch keeps the rows behind its own:
-    // the device rows live in the cache across calls, so they start from zero here
-    HIPCHK(hipMemsetAsync(tc.dx.p, 0, (size_t)B * XR_TILE * 4, st));
-    HIPCHK(hipMemsetAsync(tc.dp.p, 0, (size_t)B * KH_PSIZE * 4, st));
-    HIPCHK(hipMemsetAsync(tc.dv.p, 0, (size_t)B * 4, st));
-    float* slots = reinterpret_cast<float*>(tc.pin_loss.p);
-    call.t_setup = std::chrono::steady_clock::now();
-    size_t step = 0;
-    for (int epoch = 0; epoch < epochs; ++epoch)
-        for (int base = 0; base < n; base += B, ++step) {
-            launch_expand_records(tc.rec.as<char>(), lay, tc.order.as<int32_t>() + (size_t)epoch * n, base, std::min(B, n - base),
-                                  tc.dx.as<float>(), tc.dp.as<float>(), tc.dv.as<float>(), st);
-            HIPCHK(hipGetLastError());
-            if ((rc = train_launch_step(call))) return rc;
-            HIPCHK(hipMemcpyAsync(slots + step * slot, tc.dloss.p, slot * 4, hipMemcpyDeviceToHost, st));
-        }
-    HIPCHK(hipStreamSynchronize(st));                         // the one synchronisation of the call
-    // kh_train's bookkeeping over the steps in order: the first failing step decides status and message (nothing is
-    // installed before the end of the call, so running the later steps changed nothing that is kept)
-    float firstloss = 0.0f, lastloss = 0.0f;
-    step = 0;
-    for (int epoch = 0; epoch < epochs; ++epoch) {
-        float avgloss = 0.0f;
-        for (int b = 0; b < per_epoch; ++b, ++step) {
-            float loss;
-            if ((rc = train_step_result(call, slots + step * slot, cfg->detect_anomaly != 0, epoch, b, &loss))) return rc;
-            avgloss += loss;
-        }
-        avgloss /= (float)per_epoch;
-        if (!epoch) firstloss = avgloss;
-        lastloss = avgloss;
-    }
-    call.t_steps = std::chrono::steady_clock::now();
-    if ((rc = train_finish(e, call, n, epochs))) return rc;
-    if (first_loss) *first_loss = firstloss;
-    if (last_loss) *last_loss = lastloss;
-    return KH_OK;
+int kh_train_replay(kh_engine* e, kh_replay* r, int n, const kh_train_config* cfg, float* first_loss, float* last_loss)
+{
+    if (!e || !r || !cfg) return fail(KH_ERR_INVALID, "null argument");
+    if (n < 1 || cfg->batch < 2 || cfg->epochs < 1) return fail(KH_ERR_INVALID, "trajectories >= 1, batch >= 2, epochs >= 1 required");
+    int rc = check_records(e, "kh_train_replay");
+    if (rc) return rc;
+    if ((rc = kh_train_config_check(cfg))) return rc;
+    if (r->device != e->cfg.device)
+        return fail(KH_ERR_INVALID, "kh_train_replay: the ring is on device %d, the engine on device %d", r->device, e->cfg.device);
+    std::lock_guard<std::mutex> ring(r->mu);                  // adds wait; taken before the engine's trainer lock (train_begin)
+    return train_on_records(e, "kh_train_replay", nullptr, r, n, cfg, first_loss, last_loss);
 }
 
 }  // extern "C"

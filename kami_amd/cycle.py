@@ -10,14 +10,16 @@
 Multi-GPU: every rank plays its own shard of the trees with its own engine, rank 0 trains.
 
 With a CompactReplay ring the records stay compact all the way: the gathered payloads go into the ring as bytes and rank 0
-trains with NN.train_records (kh_train_records), which expands each batch on the device."""
+trains with NN.train_records (kh_train_records), which expands each batch on the device.  With a DeviceReplay ring
+they also stay where the collective left them: under RCCL the gathered payloads are device tensors, go into the ring
+by kh_replay_add_device and rank 0 trains with NN.train_replay (kh_train_replay) from the ring in place."""
 from __future__ import annotations
 
 import numpy as np
 
 from . import _lib as L
 from . import dist as kd
-from .replay import CompactReplay, ReplayBuffer
+from .replay import CompactReplay, DeviceReplay, ReplayBuffer
 
 OBSIZE, PSIZE = 8 * 8 * 30, 4672
 
@@ -35,7 +37,7 @@ def records_to_arrays(nn, records):
     return planes, mcts, vals
 
 
-def generation(nn, pool, replay: "ReplayBuffer | CompactReplay", *, play_evals: int, play_seconds: float = 60.0, sample: int | None = None,
+def generation(nn, pool, replay: "ReplayBuffer | CompactReplay | DeviceReplay", *, play_evals: int, play_seconds: float = 60.0, sample: int | None = None,
                mlr: int = 5, epochs: int = 8, batchsize: int = 8, momentum: float = 0.0, nesterov: bool = False,
                weight_decay: float = 0.0, max_grad_norm: float = 0.0, dist=None, device: str | None = None, gate: dict | None = None):
     """Play, collect, train (rank 0), publish.  Returns a dict of what happened.  The collectives' tensors live where
@@ -49,7 +51,8 @@ def generation(nn, pool, replay: "ReplayBuffer | CompactReplay", *, play_evals: 
     from . import search as S
     from .replay import gather_compact
     st = pool.run(min_evals=play_evals, max_seconds=play_seconds)
-    compact = isinstance(replay, CompactReplay)
+    on_device = isinstance(replay, DeviceReplay)
+    compact = on_device or isinstance(replay, CompactReplay)
     # merge over the ranks as COMPACT records (664 B each); into a dense ring the root expands them (device encoder)
     if compact:
         payload = pool.drain_bytes()
@@ -59,9 +62,14 @@ def generation(nn, pool, replay: "ReplayBuffer | CompactReplay", *, play_evals: 
         payload = b"".join(bytes(r) for r in mine)
     merged = 0
     rank0 = dist is None or dist.get_rank() == 0
-    for r, blob in enumerate(gather_compact(dist, payload, C.sizeof(S.Record), root=0, device=device)):
+    for r, blob in enumerate(gather_compact(dist, payload, C.sizeof(S.Record), root=0, device=device, as_tensor=on_device)):
         if compact:
-            added = replay.add_bytes(blob)
+            if not on_device:
+                added = replay.add_bytes(blob)
+            elif blob.is_cuda and blob.device.index == replay.device:
+                added = replay.add_tensor(blob)                              # stays in device memory under RCCL
+            else:
+                added = replay.add_bytes(blob.cpu().numpy().tobytes())
             if dist is not None and r != dist.get_rank():
                 merged += added
             continue
@@ -82,7 +90,10 @@ def generation(nn, pool, replay: "ReplayBuffer | CompactReplay", *, play_evals: 
     trainee = nn.clone() if gate is not None and rank == 0 and have >= batchsize else nn      # selfplay.cpp:259
     if rank == 0 and have >= batchsize and compact:
         n = sample or (have // batchsize) * batchsize
-        first, last = trainee.train_records(replay.select(n), mlr=mlr, epochs=epochs, batchsize=batchsize, **optim)
+        if on_device:
+            first, last = trainee.train_replay(replay, n, mlr=mlr, epochs=epochs, batchsize=batchsize, **optim)
+        else:
+            first, last = trainee.train_records(replay.select(n), mlr=mlr, epochs=epochs, batchsize=batchsize, **optim)
         out.update(first_loss=first, last_loss=last, trained_on=n)
     elif rank == 0 and have >= batchsize:
         n = sample or (have // batchsize) * batchsize

@@ -218,6 +218,16 @@ class NN:
         self._blob = self.get_weights()
         return first.value, last.value
 
+    def train_replay(self, replay, n: int, *, mlr: int = 5, epochs: int = 8, batchsize: int = 8, detect_anomaly: bool = False,
+                     momentum: float = 0.0, nesterov: bool = False, weight_decay: float = 0.0, max_grad_norm: float = 0.0):
+        """kh_train_replay: train_records(replay.select(n)) for a replay.DeviceReplay on this engine's GPU, bit for bit,
+        with the records read where they lie in device memory: only the sample order is uploaded."""
+        cfg = self._train_config(mlr, epochs, batchsize, detect_anomaly, momentum, nesterov, weight_decay, max_grad_norm)
+        first, last = C.c_float(), C.c_float()
+        _chk(self._lib.kh_train_replay(self._h, replay.handle, int(n), C.byref(cfg), C.byref(first), C.byref(last)))
+        self._blob = self.get_weights()
+        return first.value, last.value
+
     def last_grad_norms(self) -> np.ndarray:
         """kh_train_grad_norms: the gradient norm before clipping of every step of the last completed train() /
         train_records() call that ran with max_grad_norm > 0, in step order (empty if it did not clip)."""

@@ -149,15 +149,130 @@ class CompactReplay:
         self.close()
 
 
-def gather_compact(dist, payload: bytes, record_bytes: int, root: int = 0, device: str | None = None):
+class DeviceReplay:
+    """CompactReplay with the ring in device memory (kh_replay_*), on the GPU of the engine `nn`: the same slots, the
+    same draws for the same seed and calls, records validated as they are added (a failed add raises KamiError with
+    kh_records_validate's message and `.bad_index`, and changes nothing).  `add_tensor` takes records that are already
+    in device memory — the root's end of an RCCL gather — and `nn.train_replay(ring, n)` trains from the ring in place.
+    The ring outlives `nn`; any engine with features == 30 on that GPU may train from it."""
+
+    def __init__(self, nn, bufsize: int, seed: int = 0):
+        import ctypes as C
+        from . import _lib as L
+        from .nn import KamiError
+        self._C, self._L, self._err, self._dtype = C, L, KamiError, L.RECORD_DTYPE
+        self.lib = L.load()
+        self.device = nn.cfg.device
+        self.handle = C.c_void_p()
+        self._chk(self.lib.kh_replay_create(nn.handle, int(bufsize), int(seed) & (2 ** 64 - 1), C.byref(self.handle)))
+        _LIVE_RINGS.add(self)
+
+    def _chk(self, rc: int, bad=None) -> None:
+        if rc != self._L.KH_OK:
+            err = self._err(rc, self._L.last_error())
+            if bad is not None:
+                err.bad_index = bad.value
+            raise err
+
+    def add(self, records) -> int:
+        """Records in any form NN.train_records takes; returns how many went in."""
+        from .nn import as_records
+        rec = as_records(records)
+        bad = self._C.c_int(-1)
+        self._chk(self.lib.kh_replay_add(self.handle, rec.ctypes.data, rec.size, self._C.byref(bad)), bad)
+        return rec.size
+
+    def add_bytes(self, payload: bytes) -> int:
+        """A payload of whole records, as gather_compact returns them per rank."""
+        if len(payload) % self._dtype.itemsize:
+            raise ValueError(f"{len(payload)} bytes are not a whole number of {self._dtype.itemsize}-byte records")
+        return self.add(payload) if payload else 0
+
+    def add_tensor(self, t) -> int:
+        """Whole records in a contiguous uint8 CUDA tensor on the ring's GPU (anything else: ValueError), added where
+        they lie by kh_replay_add_device on torch's current stream."""
+        import torch
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+            raise ValueError(f"device records must be a uint8 tensor, not {getattr(t, 'dtype', type(t))}")
+        if not t.is_contiguous():
+            raise ValueError("device records must be contiguous")
+        if t.device.type != "cuda" or t.device.index != self.device:
+            raise ValueError(f"device records are on {t.device}, the ring on GPU {self.device}")
+        if t.numel() % self._dtype.itemsize:
+            raise ValueError(f"{t.numel()} bytes are not a whole number of {self._dtype.itemsize}-byte records")
+        n = t.numel() // self._dtype.itemsize
+        if n == 0:
+            return 0
+        stream = torch.cuda.current_stream(t.device)
+        if not stream.cuda_stream:             # the legacy default stream has no handle to order behind: drain it
+            stream.synchronize()
+        bad = self._C.c_int(-1)
+        self._chk(self.lib.kh_replay_add_device(self.handle, self._C.c_void_p(t.data_ptr()), n, self._C.c_void_p(stream.cuda_stream),
+                                                self._C.byref(bad)), bad)
+        return n
+
+    def size(self) -> int:
+        return self.lib.kh_replay_size(self.handle)
+
+    def count(self) -> int:
+        return self.lib.kh_replay_count(self.handle)
+
+    def clear(self) -> None:
+        self._chk(self.lib.kh_replay_clear(self.handle))
+
+    def read(self, first_slot: int, n: int) -> np.ndarray:
+        """Slots first_slot .. first_slot + n - 1 (mod the capacity) as a NumPy record array; no draw is made."""
+        out = np.zeros(int(n), self._dtype)
+        self._chk(self.lib.kh_replay_read(self.handle, int(first_slot), int(n), out.ctypes.data))
+        return out
+
+    def select(self, n: int) -> np.ndarray:
+        out = np.zeros(int(n), self._dtype)
+        self._chk(self.lib.kh_replay_select(self.handle, int(n), out.ctypes.data))
+        return out
+
+    def close(self) -> None:
+        if getattr(self, "handle", None):
+            self.lib.kh_replay_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# rings still open when the interpreter exits are freed while the HIP runtime is still up (as nn.py does for engines)
+import atexit
+import weakref
+
+_LIVE_RINGS = weakref.WeakSet()
+
+
+@atexit.register
+def _close_rings():
+    for ring in list(_LIVE_RINGS):
+        try:
+            ring.close()
+        except Exception:
+            pass
+
+
+def gather_compact(dist, payload: bytes, record_bytes: int, root: int = 0, device: str | None = None, as_tensor: bool = False):
     """Merge fixed-size compact records (ks_record, 664 bytes: board + sparse visit distribution + value —
     include/kami_search.h) over the ranks: 40x less traffic than the dense 26 372-byte rows `gather` moves.
     Every rank passes its own records; returns the list of every rank's payload (rank-major) on `root`, and
     [] elsewhere.  One size all-reduce + one gather of uint8 to the root (RCCL over xGMI with device tensors: the
-    root's seven direct links carry one rank's payload each; gloo on CPU)."""
+    root's seven direct links carry one rank's payload each; gloo on CPU).
+    as_tensor=True: the payloads as uint8 tensors, outs[r][:count], where the collective left them — device memory under
+    RCCL (what DeviceReplay.add_tensor takes: the records never visit the host), CPU tensors under gloo or without a
+    group."""
     import torch
     if dist is None:
-        return [payload]
+        if not as_tensor:
+            return [payload]
+        return [torch.frombuffer(bytearray(payload), dtype=torch.uint8) if payload else torch.zeros(0, dtype=torch.uint8)]
     from .dist import collective_device
     device = device or collective_device(dist)
     world, rank = dist.get_world_size(), dist.get_rank()
@@ -167,7 +282,9 @@ def gather_compact(dist, payload: bytes, record_bytes: int, root: int = 0, devic
     dist.all_reduce(counts)
     nmax = int(counts.max().item())
     if nmax == 0:
-        return [b""] * world if rank == root else []
+        if rank != root:
+            return []
+        return [torch.zeros(0, dtype=torch.uint8, device=device) for _ in range(world)] if as_tensor else [b""] * world
     pad = torch.zeros(nmax, dtype=torch.uint8, device=device)
     if payload:
         pad[:len(payload)] = torch.frombuffer(bytearray(payload), dtype=torch.uint8).to(device)
@@ -175,4 +292,6 @@ def gather_compact(dist, payload: bytes, record_bytes: int, root: int = 0, devic
     dist.gather(pad, gather_list=outs, dst=root)
     if rank != root:
         return []
+    if as_tensor:
+        return [outs[r][:int(counts[r].item())] for r in range(world)]
     return [outs[r][:int(counts[r].item())].cpu().numpy().tobytes() for r in range(world)]
