@@ -262,6 +262,47 @@ int     kh_replay_select(kh_replay* r, int n, kh_record* out);
 int     kh_train_replay(kh_engine* e, kh_replay* r, int n, const kh_train_config* cfg,
                         float* first_loss, float* last_loss);
 
+/* ---- held-out loss: the network as served, measured on compact records ------------------------------------------
+ * For each of n records the engine's serving forward — the internal path of kh_encode_infer_device: the engine's dtype,
+ * inference-mode BatchNorm (running statistics), the existing kernel dispatch, at most KH_EVAL_CHUNK boards per launch
+ * in record order — leaves policy p[4672] and value v[256] in device memory, and a HIP kernel computes there, in double:
+ *   Lp_i    = - sum_{k < nact_i} visits_ik * log(p_i[actions_ik] + 0.001)       (0 when nact_i == 0)
+ *   Lv_i    = (1 / 256) sum_j (v_ij - value_i)^2                                 (the target broadcast, as nn.cpp:96 does)
+ *   agree_i = 1 when nact_i > 0 and the entry with the largest visits_ik is the entry with the largest p_i[actions_ik]
+ *             (fp32 comparisons, the first maximum in entry order on both sides), else 0
+ * A record's three results depend on that record and the forward's two rows for it alone; the totals are summed in an
+ * order that depends on n alone (per chunk of KH_EVAL_CHUNK records on the device, the chunks in order on the host).
+ *   Relation to the trainer's figure: for a batch of B records kh_train* reports B * policy_loss + value_loss of that
+ * batch, computed with BatchNorm on BATCH statistics, in fp32, with logf(p + 0.001f), on the samples it is about to
+ * step on.  kh_eval_* measures the network that plays, on records of the caller's choosing, and changes nothing: no
+ * training-mode arithmetic, weights, kh_generation and kh_bn_batches stay as they are.  All chunks run on the parameter
+ * set that was current when the call began; result.generation is that set's.  May run from any thread beside kh_infer*
+ * (it takes the device calls' lock).  One host synchronisation per call.
+ *   Status: KH_ERR_INVALID — null e / records / ring / out, n < 1, cfg.features != 30, records kh_records_validate
+ * rejects (its message), first_slot outside [0, capacity), n outside [1, capacity], a ring on another device — all
+ * decided before any device work; KH_ERR_NO_WEIGHTS before kh_load_weights; KH_ERR_NAN_POLICY / KH_ERR_NAN_VALUE with
+ * kh_infer's messages when the NETWORK's outputs hold a NaN (policy first, as in kh_infer; *out is not written).
+ * Non-finite visits / value of the records themselves are no error: they propagate under IEEE rules (top1 is then
+ * unspecified for such records). */
+#define KH_EVAL_CHUNK 1024            /* positions per forward launch inside kh_eval_*; scratch is bounded by it */
+typedef struct kh_eval_result {
+    int64_t records;         /* n */
+    int64_t policy_records;  /* records with nact > 0 */
+    double  policy_loss;     /* (1/n) sum Lp_i */
+    double  value_loss;      /* (1/n) sum Lv_i */
+    double  top1;            /* sum agree_i / policy_records; 0 when policy_records == 0 */
+    int32_t generation;      /* of the parameter set that was evaluated */
+    int32_t reserved[5];     /* zero */
+} kh_eval_result;            /* 64 bytes */
+/* n host records, validated, uploaded once.  record_policy_loss / record_value_loss: Lp_i / Lv_i, [n] each, nullable. */
+int  kh_eval_records(kh_engine* e, const kh_record* rec, int n, kh_eval_result* out,
+                     double* record_policy_loss, double* record_value_loss);
+/* The same over slots first_slot .. first_slot + n - 1 (mod capacity) of a device ring, read where they lie (a
+ * contiguous span's boards go to the forward straight from the ring; a launch is cut where the ring wraps).  No draw is
+ * made: head, count and the generator are untouched.  Holds the ring's mutex like kh_train_replay. */
+int  kh_eval_replay(kh_engine* e, kh_replay* r, int first_slot, int n, kh_eval_result* out,
+                    double* record_policy_loss, double* record_value_loss);
+
 /* NN::read nn.cpp:204-222: parse a checkpoint file without an engine.  Two containers are understood:
  * the reference's own — the libtorch archive NN::write leaves (nn.cpp:189-202: module.save + the
  * "generation" IValue), read here with a zip walk and a pickle stack machine (csrc/torch_archive.h; no

@@ -58,6 +58,19 @@ class TrainConfig(C.Structure):
                 ("momentum", C.c_float), ("weight_decay", C.c_float), ("max_grad_norm", C.c_float), ("nesterov", C.c_int32)]
 
 
+class EvalResult(C.Structure):
+    """kh_eval_result (64 bytes): what kh_eval_records / kh_eval_replay report."""
+    _fields_ = [("records", C.c_int64), ("policy_records", C.c_int64), ("policy_loss", C.c_double), ("value_loss", C.c_double),
+                ("top1", C.c_double), ("generation", C.c_int32), ("reserved", C.c_int32 * 5)]
+
+
+# numpy view of kh_eval_result
+EVAL_DTYPE = np.dtype([("records", "<i8"), ("policy_records", "<i8"), ("policy_loss", "<f8"), ("value_loss", "<f8"),
+                       ("top1", "<f8"), ("generation", "<i4"), ("reserved", "<i4", (5,))])
+EVAL_CHUNK = 1024        # KH_EVAL_CHUNK
+assert C.sizeof(EvalResult) == 64 and EVAL_DTYPE.itemsize == 64
+
+
 SYMBOLS = {
     "kh_weight_count": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "kh_create": (C.c_int, [C.POINTER(Config), C.POINTER(_P)]),
@@ -82,6 +95,8 @@ SYMBOLS = {
     "kh_replay_read": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "kh_replay_select": (C.c_int, [_P, C.c_int, _P]),
     "kh_train_replay": (C.c_int, [_P, _P, C.c_int, C.POINTER(TrainConfig), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "kh_eval_records": (C.c_int, [_P, _P, C.c_int, C.POINTER(EvalResult), _P, _P]),
+    "kh_eval_replay": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(EvalResult), _P, _P]),
     "kh_checkpoint_read": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                      _P, C.c_size_t, C.POINTER(C.c_size_t)]),
     "kh_checkpoint_read_ex": (C.c_int, [C.c_char_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int),

@@ -21,12 +21,14 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libkamihip.so")
 ARCH = "gfx950"
-SOURCES = ["kh_api.hip", "weights.hip", "weights_pack.hip", "queue.hip", "encode.hip", "forward_simple.hip", "tower_mfma.hip", "tower8_mfma.hip", "layers_mfma.hip", "train.hip", "train_ingest.hip", "replay_ring.hip"]
+SOURCES = ["kh_api.hip", "weights.hip", "weights_pack.hip", "queue.hip", "encode.hip", "forward_simple.hip", "tower_mfma.hip", "tower8_mfma.hip", "layers_mfma.hip", "train.hip", "train_ingest.hip", "replay_ring.hip", "eval.hip"]
 # MFMA results in arch VGPRs: the epilogues read them with VALU ops and would otherwise pay a
 # v_accvgpr_read per value (the kernel runs one wave per SIMD, registers are not scarce).
 # weights_pack.hip: the device packer folds BatchNorm with the host packer's three roundings (subtract, multiply, add);
 # under -ffp-contract=fast the multiply and the add fuse and a shift's last bit changes.  (Later flags win.)
-EXTRA_FLAGS = {"tower8_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "weights_pack.hip": ["-ffp-contract=off"]}
+# eval.hip: the losses are stated as products rounded to double, then added; no fused multiply-add.
+EXTRA_FLAGS = {"tower8_mfma.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "weights_pack.hip": ["-ffp-contract=off"],
+               "eval.hip": ["-ffp-contract=off"]}
 HIPCC_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-result", "-Wno-pass-failed",
                "-ffp-contract=fast"]
 

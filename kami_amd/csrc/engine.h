@@ -1,6 +1,6 @@
 // engine.h — the engine's host-side state and the declarations its translation units share: kh_api.hip (C ABI, slots,
 // forward wrappers, host and device I/O, kh_train, checkpoints), weights.hip (parameter sets; weights_pack.hip: their device packer), queue.hip (the
-// coalescing queue) and train_ingest.hip (kh_train_records, kh_expand_records).  Not part of the public boundary (that
+// coalescing queue), train_ingest.hip (kh_train_records, kh_expand_records) and eval.hip (kh_eval_*).  Not part of the public boundary (that
 // is include/kami_hip.h).
 #pragma once
 #include "kh_internal.h"
@@ -108,6 +108,13 @@ struct Slot {
 
 struct Queue;           // the submit / wait queue (queue.hip)
 
+// kh_eval_* (eval.hip): the serving forward's outputs for one chunk of KH_EVAL_CHUNK positions, the chunk's per-record
+// results and the call's per-chunk sums; kh_eval_records' record block.  Used under the engine's dmu.
+struct EvalCache {
+    DevMem policy, vfull, rows, parts, flags, rec;
+    PinMem pin_rec, pin_out;
+};
+
 // The trainer's workspace, shared by kh_train (kh_api.hip) and kh_train_records (train_ingest.hip): both write a batch
 // into dx / dp / dv and run the same recorded step on it, so alternating them on one engine re-records nothing.
 struct TrainCache {
@@ -155,6 +162,7 @@ struct kh_engine {
     std::vector<std::unique_ptr<kh::Slot>> slots;
     std::unique_ptr<kh::Slot> devslot;           // scratch for the device-pointer API
     std::mutex dmu;
+    kh::EvalCache eval;                          // kh_eval_*'s scratch (under dmu)
     kh::Queue* co = nullptr;          // submit / wait queue (created on first use)
     std::atomic<kh::Queue*> co_ready{ nullptr };     // the same pointer once the dispatcher runs: submitters skip co_mu
     std::atomic<bool> has_weights{ false };
@@ -218,6 +226,11 @@ int forward_tower(kh_engine* e, const Weights& W, Slot& s, hipStream_t st, const
 int forward_dispatch(kh_engine* e, const Weights& W, Slot& s, hipStream_t st, const float* d_in, int B,
                      float* d_policy, float* d_vfull, float* d_logits_out);
 bool fused_ingest(const kh_engine* e, const Weights& W);
+// kh_encode_infer_device behind its argument checks, e->dmu held by the caller: the serving forward on `batch` compact
+// boards in device memory (fused ingest where the engine has it, the encode kernel into scratch otherwise).  *st_out: the
+// stream it went to (`stream`, or the engine's own for nullptr)
+int encode_infer_on_device(kh_engine* e, const Weights& W, const kh_board* d_boards, int batch, float* d_policy, float* d_vfull,
+                           void* stream, hipStream_t* st_out);
 
 // One host-buffer inference call (kh_infer*, the queue's synchronous kinds): planes [batch][8][8][F] or compact records
 // in; the outputs the caller wants (null: not wanted), `value` by value_mode, `legal` the priors of the legal actions.

@@ -1139,6 +1139,27 @@ int kh_encode_device(kh_engine* e, const kh_board* d_boards, int batch, float* d
     return KH_OK;
 }
 
+}  // extern "C"
+
+namespace kh {
+int encode_infer_on_device(kh_engine* e, const Weights& W, const kh_board* d_boards, int batch, float* d_policy, float* d_vfull,
+                           void* stream, hipStream_t* st_out)
+{
+    Slot* s;
+    hipStream_t st;
+    int rc = dev_slot(e, batch, stream, &s, &st);
+    if (rc) return rc;
+    *st_out = st;
+    if (fused_ingest(e, W)) return forward_tower(e, W, *s, st, nullptr, batch, d_policy, d_vfull, nullptr, d_boards);
+    if (s->planes.ensure((size_t)batch * 64 * KH_NFEATURES * 4)) return KH_ERR_HIP;
+    kh::launch_encode_f32(d_boards, batch, s->planes.as<float>(), st);
+    if ((rc = forward_dispatch(e, W, *s, st, s->planes.as<float>(), batch, d_policy, d_vfull, nullptr))) return rc;
+    return dev_slot_done(e, W, *s, st);
+}
+}  // namespace kh
+
+extern "C" {
+
 int kh_encode_infer_device(kh_engine* e, const kh_board* d_boards, int batch, float* d_policy,
                            float* d_value_full, void* stream)
 {
@@ -1150,14 +1171,8 @@ int kh_encode_infer_device(kh_engine* e, const kh_board* d_boards, int batch, fl
     if (!W) return fail(KH_ERR_NO_WEIGHTS, "kh_encode_infer_device before kh_load_weights");
     if ((rc = set_device(e))) return rc;
     std::lock_guard<std::mutex> lk(e->dmu);
-    Slot* s;
     hipStream_t st;
-    if ((rc = dev_slot(e, batch, stream, &s, &st))) return rc;
-    if (fused_ingest(e, *W)) return forward_tower(e, *W, *s, st, nullptr, batch, d_policy, d_value_full, nullptr, d_boards);
-    if (s->planes.ensure((size_t)batch * 64 * KH_NFEATURES * 4)) return KH_ERR_HIP;
-    kh::launch_encode_f32(d_boards, batch, s->planes.as<float>(), st);
-    if ((rc = forward_dispatch(e, *W, *s, st, s->planes.as<float>(), batch, d_policy, d_value_full, nullptr))) return rc;
-    return dev_slot_done(e, *W, *s, st);
+    return kh::encode_infer_on_device(e, *W, d_boards, batch, d_policy, d_value_full, stream, &st);
 }
 
 static int time_loop(kh_engine* e, int iters, float* ms, int (*body)(void*), void* ctx)

@@ -119,6 +119,25 @@ def validate_records(records) -> int:
     return rec.size
 
 
+class EvalResult:
+    """What NN.eval_records / NN.eval_replay return (kh_eval_result): `records`, `policy_records` (those with nact > 0),
+    `policy_loss` and `value_loss` (means over the records, in double), `top1` (share of policy_records whose most
+    visited move is the network's most likely one among the record's moves), `generation` of the evaluated weights.
+    With per_record=True also `record_policy_loss` / `record_value_loss`, float64 [records]; None otherwise."""
+    FIELDS = ("records", "policy_records", "policy_loss", "value_loss", "top1", "generation")
+
+    def __init__(self, res, record_policy_loss=None, record_value_loss=None):
+        for f in self.FIELDS:
+            setattr(self, f, getattr(res, f))
+        self.record_policy_loss, self.record_value_loss = record_policy_loss, record_value_loss
+
+    def as_dict(self) -> dict:
+        return {f: getattr(self, f) for f in self.FIELDS}
+
+    def __repr__(self):
+        return "EvalResult(" + ", ".join(f"{f}={getattr(self, f)!r}" for f in self.FIELDS) + ")"
+
+
 class Ticket:
     """An outstanding kh_submit_*: keeps the caller-side buffers alive until wait() (the engine reads and writes them)."""
 
@@ -227,6 +246,32 @@ class NN:
         _chk(self._lib.kh_train_replay(self._h, replay.handle, int(n), C.byref(cfg), C.byref(first), C.byref(last)))
         self._blob = self.get_weights()
         return first.value, last.value
+
+    def eval_records(self, records, per_record: bool = False) -> "EvalResult":
+        """kh_eval_records: the loss of the network AS SERVED (this engine's dtype, inference-mode BatchNorm) on compact
+        records (as_records: ctypes, bytes or NumPy), computed on the device in double.  Changes nothing: weights,
+        generation and bn_batches() stay.  -> EvalResult."""
+        rec = as_records(records)
+        return self._eval(rec.size, per_record, lambda res, lp, lv: self._lib.kh_eval_records(self._h, _ptr(rec), rec.size, res, lp, lv))
+
+    def eval_replay(self, ring, first_slot: int = 0, n: Optional[int] = None, per_record: bool = False) -> "EvalResult":
+        """kh_eval_replay: eval_records(ring.read(first_slot, n)) for a replay.DeviceReplay on this engine's GPU, bit for
+        bit, with the records read where they lie; no draw is made.  n=None: the written slots, min(count, size) — an
+        empty ring raises ValueError."""
+        if n is None:
+            n = min(ring.count(), ring.size())
+            if n == 0:
+                raise ValueError("eval_replay on an empty ring")
+        n = int(n)
+        return self._eval(n, per_record,
+                          lambda res, lp, lv: self._lib.kh_eval_replay(self._h, ring.handle, int(first_slot), n, res, lp, lv))
+
+    def _eval(self, n, per_record, call) -> "EvalResult":
+        res = L.EvalResult()
+        lp = np.zeros(max(n, 0), np.float64) if per_record else None
+        lv = np.zeros(max(n, 0), np.float64) if per_record else None
+        _chk(call(C.byref(res), _ptr(lp) if per_record else None, _ptr(lv) if per_record else None))
+        return EvalResult(res, lp, lv)
 
     def last_grad_norms(self) -> np.ndarray:
         """kh_train_grad_norms: the gradient norm before clipping of every step of the last completed train() /
