@@ -61,7 +61,11 @@ def random_weights(features: int, filters: int, residuals: int, seed: int = 0,
     """Seeded synthetic parameters (there are no checkpoints to load offline):
     conv / linear weights and biases uniform(-k, k), k = 1/sqrt(fan_in); BatchNorm gamma and
     running_var in [0.9, 1.1], beta and running_mean in [-0.1, 0.1] so that BN folding is
-    exercised.  peaky > 1 scales policyconv2.weight to give a non-flat policy."""
+    exercised.  peaky > 1 scales policyconv2.weight to give a non-flat policy.
+    The value head of such a blob is often dead: vbatchnorm has one channel, so one draw of its shift decides the sign
+    of the whole value plane, and the value row is then tanh(valuefc.bias) for every input (measured table: DESIGN.md
+    6.1; tests/_forward_ref.py::live_value_blob makes a live one).  What is generated stays as it is: seeded fixtures
+    and recorded maxima depend on it."""
     rng = np.random.default_rng(seed)
     parts = []
     fan_in = 1
